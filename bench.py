@@ -6,16 +6,24 @@ A "step" is one MCMC iteration of one chain = the reference loop body mcmc.c:210
 packed genotypes and the sampler state already resident in HBM.  Workload: BASELINE.json config 3,
 N=10000 individuals x L=5000 loci, K=5, diploid, mode 2 (-v 2 -e 1 -y 1), synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1, one chain per GPU)
 
 `value` is measured on the REPLAY schedule (stream positions identical to the reference: Z, allele
 counts, generations and seeds are bit-identical to the reference run with the same seeds), over EXACTLY
-K steps with the per-kernel profiling OFF; a second, profiled pass of the same chain gives `kernels_ms`
-and the roofline entries (HIP events on the launch stream).  The same JSON line carries the KEYED
-schedule (counter-based positions, all consumers concurrent) under "keyed" and BASELINE config 5
-(ploidy 4) under "ploidy4".  Rank 0 at N=1 also times the reference's own CPU sweeps on the host
-cores ("cpu_baseline").
+K steps with the per-kernel profiling OFF.  A plain run does nothing else: set-up, W warm-up steps, the
+K timed steps, the outputs (--dump-outputs) and the JSON line.
+
+--full adds what takes runs of its own: a second, profiled pass of the same chain gives `kernels_ms`
+and the roofline entries (HIP events on the launch stream); the same JSON line carries the KEYED
+schedule (counter-based positions, all consumers concurrent) under "keyed", several chains on one GPU
+under "concurrent_chains" and BASELINE config 5 (ploidy 4) under "ploidy4".  Rank 0 at N=1 also times
+the reference's own CPU sweeps on the host cores ("cpu_baseline").
+
+--dump-outputs DIR writes the chain state the timed steps left (rank 0, replay schedule) as DIR/<name>.npy
+in float64 / float32: what a caller of the sampler reads back after the last timed iteration.  Z is
+N*L*P cells (400 MB at config 3), so a fixed, seeded sample of its cells goes out (`z_sample` at the flat
+indices `z_sample_index`); `qqnum` holds its per-individual cluster counts in full.
 """
 from __future__ import annotations
 
@@ -40,11 +48,27 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PROFILED_STEPS = 20    # the second pass: per-kernel times
+Z_SAMPLE = 1 << 20     # cells of Z written by --dump-outputs
 
 
 def sync():
     import torch
     torch.cuda.synchronize()
+
+
+def dump_outputs(chain, out_dir):
+    """the state a caller reads back after the last timed iteration, as out_dir/<name>.npy (float64; the Z sample float32)"""
+    os.makedirs(out_dir, exist_ok=True)
+    z = chain.z().reshape(-1)
+    idx = np.unique(np.random.default_rng(20260101).integers(0, z.size, size=min(Z_SAMPLE, z.size)))
+    arrays = {
+        "qq": chain.qq(), "qqnum": chain.qqnum(), "freq": chain.freq(), "generation": chain.generation(),
+        "self_rates": chain.self_rates(), "indvlkh": chain.indvlkh(), "alpha": [chain.alpha()], "totallkh": [chain.totallkh()],
+        "seeds": chain.seeds(), "z_sample_index": idx,
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    np.save(os.path.join(out_dir, "z_sample.npy"), z[idx].astype(np.float32))
 
 
 def note(msg):
@@ -55,8 +79,9 @@ def note(msg):
 T_START = time.perf_counter()
 
 
-def timed_steps(chain, steps, warmup, world):
-    """(seconds for exactly `steps` iterations, profiling off; log-likelihood samples; per-kernel profile of a second pass)"""
+def timed_steps(chain, steps, warmup, world, full=True, dump_dir=None):
+    """(seconds for exactly `steps` iterations, profiling off; log-likelihood samples; per-kernel profile of a second pass)
+    The state after the timed steps goes to `dump_dir` when given; without `full` the samples and the profile are None."""
     import torch.distributed as dist
     chain.run(warmup)
     chain.profile(False)
@@ -72,6 +97,10 @@ def timed_steps(chain, steps, warmup, world):
     dt = time.perf_counter() - t0
     if world > 1:
         dt = multichain.max_over_ranks(dt)
+    if dump_dir:
+        dump_outputs(chain, dump_dir)
+    if not full:
+        return dt, None, None
     # second pass, same chain, per-kernel HIP events on (not part of `value`)
     chain.profile_reset()
     chain.profile(True)
@@ -387,10 +416,12 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-keyed", action="store_true")
-    ap.add_argument("--no-tetra", action="store_true", help="skip the ploidy 4 (config 5) leg")
-    ap.add_argument("--no-concurrent", action="store_true", help="skip the several-chains-on-one-GPU leg (profiling: keeps per-kernel averages single-chain)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the timed steps left as DIR/<name>.npy (rank 0, replay schedule)")
+    ap.add_argument("--full", action="store_true", help="also the profiled pass, roofline, keyed schedule, CPU baselines, concurrent chains and ploidy 4 legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-keyed", action="store_true", help="--full: skip the keyed schedule")
+    ap.add_argument("--no-tetra", action="store_true", help="--full: skip the ploidy 4 (config 5) leg")
+    ap.add_argument("--no-concurrent", action="store_true", help="--full: skip the several-chains-on-one-GPU leg (profiling: keeps per-kernel averages single-chain)")
     ap.add_argument("--chain-worker", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--device", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--rendezvous", default=None, help=argparse.SUPPRESS)
@@ -423,49 +454,40 @@ def main():
     geno, an, mi = synth.make_diploid(w["N"], w["L"], K)
     N, L, P = geno.shape
     seeds = multichain.rank_seeds((13, 4, 1972), rank)
-    traffic = load_traffic()
+    traffic = load_traffic() if args.full else {}
     out = {}
-    scheds = [("replay", capi.SCHED_REPLAY)] + ([] if args.no_keyed else [("keyed", capi.SCHED_KEYED)])
+    scheds = [("replay", capi.SCHED_REPLAY)] + ([] if args.no_keyed or not args.full else [("keyed", capi.SCHED_KEYED)])
     for tag, sched in scheds:
         if rank == 0:
             note(tag + " schedule")
         ch = capi.HipChain(geno, an, mi, K, mode=2, type_freq=1, back_refl=1, rng_sched=sched, device=local)
         ch.setseeds(*seeds)
         ch.chain_init(np.array([ch.ran1() for _ in range(K)], dtype=np.float32))
-        dt, lk, prof = timed_steps(ch, args.steps, args.warmup, world)
-        extra = {"table_bytes_Z": ch.zq_spec_stats().get("table_bytes", 0), "table_bytes_P": ch.p_device_stats()["table_bytes"]}
-        rl = roofline_of(prof, PROFILED_STEPS, N, L, P, 0, extra, traffic, 2 * N * L * P)
-        if sched == capi.SCHED_REPLAY:
-            rl["interval_resolver"] = ch.zq_spec_stats()
-            rl["update_P_device"] = ch.p_device_stats()
-            rl["block_resolver"] = ch.zq_resolve_stats()
-            rl["fallback_sweeps"] = ch.zq_fallbacks()
-        ckrep = min(len(lk), 20)
-        gr = None
-        if world > 1:
-            gr = multichain.gelman_rubin_all_ranks(np.array(lk[-ckrep:]))  # RCCL all-gather over xGMI
-        out[tag] = dict(value=world * args.steps / dt, ms_per_step=dt / args.steps * 1e3, roofline=rl, gelman_rubin=gr,
-                        kernels_ms={k: round(ms / n, 4) for k, (ms, n) in sorted(prof.items())},
-                        kernels_ms_per_step={k: round(ms / PROFILED_STEPS, 4) for k, (ms, n) in sorted(prof.items())},
+        dump_dir = args.dump_outputs if (rank == 0 and sched == capi.SCHED_REPLAY) else None
+        dt, lk, prof = timed_steps(ch, args.steps, args.warmup, world, args.full, dump_dir)
+        out[tag] = dict(value=world * args.steps / dt, ms_per_step=dt / args.steps * 1e3,
                         # whole iteration against the fused-design contract figure 3*N*L*P bytes
-                        iteration_frac_of_hbm=round(3 * N * L * P / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 6),
-                        last_totallkh=lk[-1])
+                        iteration_frac_of_hbm=round(3 * N * L * P / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 6))
+        if args.full:
+            extra = {"table_bytes_Z": ch.zq_spec_stats().get("table_bytes", 0), "table_bytes_P": ch.p_device_stats()["table_bytes"]}
+            rl = roofline_of(prof, PROFILED_STEPS, N, L, P, 0, extra, traffic, 2 * N * L * P)
+            if sched == capi.SCHED_REPLAY:
+                rl["interval_resolver"] = ch.zq_spec_stats()
+                rl["update_P_device"] = ch.p_device_stats()
+                rl["block_resolver"] = ch.zq_resolve_stats()
+                rl["fallback_sweeps"] = ch.zq_fallbacks()
+            ckrep = min(len(lk), 20)
+            gr = None
+            if world > 1:
+                gr = multichain.gelman_rubin_all_ranks(np.array(lk[-ckrep:]))  # RCCL all-gather over xGMI
+            out[tag].update(roofline=rl, gelman_rubin=gr,
+                            kernels_ms={k: round(ms / n, 4) for k, (ms, n) in sorted(prof.items())},
+                            kernels_ms_per_step={k: round(ms / PROFILED_STEPS, 4) for k, (ms, n) in sorted(prof.items())},
+                            last_totallkh=lk[-1])
         ch.close()
 
     if rank == 0:
-        cpu = cpu8 = None
-        if world == 1 and not args.no_cpu:
-            note("cpu baseline: one reference process")
-            cpu = cpu_baseline(geno, K, seeds)
-            note("cpu baseline: eight reference processes")
-            cpu8 = cpu_baseline_concurrent(geno, K, seeds)
-        note("copy bandwidth")
         head = out["replay"]
-        copy_gbs = round(capi.copy_bandwidth(local), 1)  # the fraction against a measured device-to-device copy as well (16-byte accesses)
-        for o in out.values():
-            o["roofline"]["copy_peak_measured"] = copy_gbs
-            if o["roofline"].get("achieved"):
-                o["roofline"]["frac_of_measured_copy"] = round(o["roofline"]["achieved"] / copy_gbs, 6)
         line = {
             "metric": "MCMC iterations/sec (update_P+update_ZQ+update_SG) at NxLxK", "value": round(head["value"], 4),
             "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -473,27 +495,44 @@ def main():
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": w["name"], "N": N, "L": L, "K": K, "ploidy": P, "mode": 2, "rng_schedule": "replay",
                        "chains": world, "parallelism": f"{world} independent chain(s), one per GPU"},
-            "roofline": head["roofline"], "cpu_baseline": cpu, "cpu_baseline_8_processes": cpu8,
-            "speedup_vs_cpu": (round(head["value"] / world / cpu["value"], 2) if cpu else None),
-            "kernels_ms": head["kernels_ms"], "kernels_ms_per_step": head["kernels_ms_per_step"], "iteration_frac_of_hbm": head["iteration_frac_of_hbm"],
-            "gelman_rubin": head["gelman_rubin"],
-            "timing": f"value: exactly {args.steps} iterations after {args.warmup} warm-up, per-kernel events off; kernels_ms / roofline: a second pass of {PROFILED_STEPS} iterations with events on",
+            "iteration_frac_of_hbm": head["iteration_frac_of_hbm"],
+            "timing": f"value: exactly {args.steps} iterations after {args.warmup} warm-up, per-kernel events off",
         }
-        if "keyed" in out:
-            k = out["keyed"]
-            line["keyed"] = {"value": round(k["value"], 4), "unit": "iterations/s", "ms_per_step": round(k["ms_per_step"], 4),
-                             "roofline": k["roofline"], "kernels_ms": k["kernels_ms"], "iteration_frac_of_hbm": k["iteration_frac_of_hbm"],
-                             "speedup_vs_cpu": (round(k["value"] / world / cpu["value"], 2) if cpu else None),
-                             "gelman_rubin": k["gelman_rubin"],
-                             "note": "counter-based stream positions: bit-identical to the oracle's keyed schedule, statistically equivalent to the reference"}
-        if world == 1 and not args.no_tetra:
-            if not args.no_concurrent:
-                note("several chains on one GPU: threads, then processes")
-                line["concurrent_chains"] = concurrent_chains_leg(geno, an, mi, K, local, max(10, args.steps // 4), args.workload)
-                if cpu8 and line["concurrent_chains"].get("processes"):  # several chains on ONE GPU against eight host cores
-                    line["concurrent_chains"]["processes"]["vs_cpu_8_processes"] = round(line["concurrent_chains"]["processes"]["chain_iterations_per_s"] / cpu8["value"], 1)
-            note("ploidy 4 (config 5)")
-            line["ploidy4"] = tetra_leg(local, max(4, args.steps // 10), 2, not args.no_cpu)
+        if args.full:
+            cpu = cpu8 = None
+            if world == 1 and not args.no_cpu:
+                note("cpu baseline: one reference process")
+                cpu = cpu_baseline(geno, K, seeds)
+                note("cpu baseline: eight reference processes")
+                cpu8 = cpu_baseline_concurrent(geno, K, seeds)
+            note("copy bandwidth")
+            copy_gbs = round(capi.copy_bandwidth(local), 1)  # the fraction against a measured device-to-device copy as well (16-byte accesses)
+            for o in out.values():
+                o["roofline"]["copy_peak_measured"] = copy_gbs
+                if o["roofline"].get("achieved"):
+                    o["roofline"]["frac_of_measured_copy"] = round(o["roofline"]["achieved"] / copy_gbs, 6)
+            line.update({
+                "roofline": head["roofline"], "cpu_baseline": cpu, "cpu_baseline_8_processes": cpu8,
+                "speedup_vs_cpu": (round(head["value"] / world / cpu["value"], 2) if cpu else None),
+                "kernels_ms": head["kernels_ms"], "kernels_ms_per_step": head["kernels_ms_per_step"],
+                "gelman_rubin": head["gelman_rubin"],
+                "timing": line["timing"] + f"; kernels_ms / roofline: a second pass of {PROFILED_STEPS} iterations with events on",
+            })
+            if "keyed" in out:
+                k = out["keyed"]
+                line["keyed"] = {"value": round(k["value"], 4), "unit": "iterations/s", "ms_per_step": round(k["ms_per_step"], 4),
+                                 "roofline": k["roofline"], "kernels_ms": k["kernels_ms"], "iteration_frac_of_hbm": k["iteration_frac_of_hbm"],
+                                 "speedup_vs_cpu": (round(k["value"] / world / cpu["value"], 2) if cpu else None),
+                                 "gelman_rubin": k["gelman_rubin"],
+                                 "note": "counter-based stream positions: bit-identical to the oracle's keyed schedule, statistically equivalent to the reference"}
+            if world == 1 and not args.no_tetra:
+                if not args.no_concurrent:
+                    note("several chains on one GPU: threads, then processes")
+                    line["concurrent_chains"] = concurrent_chains_leg(geno, an, mi, K, local, max(10, args.steps // 4), args.workload)
+                    if cpu8 and line["concurrent_chains"].get("processes"):  # several chains on ONE GPU against eight host cores
+                        line["concurrent_chains"]["processes"]["vs_cpu_8_processes"] = round(line["concurrent_chains"]["processes"]["chain_iterations_per_s"] / cpu8["value"], 1)
+                note("ploidy 4 (config 5)")
+                line["ploidy4"] = tetra_leg(local, max(4, args.steps // 10), 2, not args.no_cpu)
         note("done")
         print(json.dumps(line), flush=True)
     if world > 1:

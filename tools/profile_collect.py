@@ -13,7 +13,7 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = os.path.join(ROOT, "gpurun_out")
+out = os.environ.get("TOOL_OUT", os.path.join(ROOT, "tool_out"))  # where tools/profile_round.sh wrote
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r03"
 
 SHORT = [("k_wk_table<0>", "k_wk_table_P"), ("k_wk_table<1>", "k_wk_table_Z"), ("k_zq_at", "k_zq_at"), ("k_zq_probe", "k_zq_probe"), ("k4_zq_probe", "k4_zq_probe"),
