@@ -43,7 +43,7 @@ typedef struct {
 	int32_t N;         /* individuals            SEQDATA.totalsize */
 	int32_t L;         /* polymorphic loci       SEQDATA.locinum   */
 	int32_t P;         /* ploidy (2)             SEQDATA.ploid     */
-	int32_t K;         /* clusters (<= 32)       SEQDATA.popnum    */
+	int32_t K;         /* clusters (<= 64; ploidy 4: <= 32)  SEQDATA.popnum */
 	int32_t mode;      /* 0 no admixture, 1 admixture, 2 population selfing rates, 3 individual selfing rates, 4 / 5 population / individual inbreeding coefficients (InStruct.c:58, mcmc.c:63-87) */
 	int32_t type_freq; /* -y (InStruct.c:46) */
 	int32_t back_refl; /* -e (InStruct.c:45) */

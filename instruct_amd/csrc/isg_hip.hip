@@ -38,12 +38,14 @@
 #include <thread>
 #include <vector>
 #include <new>
+#include <type_traits>
 #include "../../include/instruct_hip.h"
 #include "isg_math.h"
 #include "isg_wh.h"
 #include "isg_sampler.h"
 
-#define ISG_KCAP 32
+#define ISG_KCAP 32  /* K of the register-resident kernel instances, and of ploidy 4 */
+#define ISG_KWIDE 64 /* diploid K above ISG_KCAP: the K-generic wide kernels (DESIGN.md §4 "K up to 64") */
 #define ISG_LPT 4 /* loci per lane per pass: 8 bytes of geno + 8 bytes of z */
 
 static thread_local std::string g_err;
@@ -433,6 +435,51 @@ __global__ void __launch_bounds__(BLOCK) k_gprop(DevView d, const double *S, isg
 	}
 	if (threadIdx.x == 0) *pos_out = (uint64_t)d.N + running;
 }
+/* K > ISG_KCAP: the same with the wide cap (a body shared with k_gprop through a template changed k_gprop's register allocation) */
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_gprop_w(DevView d, const double *S, isg_wh base, int keyed, uint64_t *pos_out)
+{
+	__shared__ unsigned sm[BLOCK / 64 + 1];
+	__shared__ double Ssh[ISG_KWIDE];
+	const bool indiv = (d.mode == 3); /* mode 3: S has one selfing rate per individual (mcmc.c:1069-1070) */
+	if (!indiv && threadIdx.x < (unsigned)d.K) Ssh[threadIdx.x] = S[threadIdx.x];
+	__syncthreads();
+	unsigned running = 0;
+	for (int i0 = 0; i0 < d.N; i0 += BLOCK) {
+		int i = i0 + threadIdx.x;
+		double selfing = 0;
+		int stat = 0;
+		if (i < d.N) {
+			if (indiv) selfing = S[i];
+			else for (int k = 0; k < d.K; k++) selfing += d.qq[(size_t)i * d.K + k] * Ssh[k];
+			stat = isg_dt_stat(selfing);
+			if (stat < 0) { /* mcmc.c:1540-1541: the reference prints the value and exits; the host does that after this launch */
+				if ((atomicOr(d.err, 2u) & 2u) == 0u) *(double *)(d.err + 2) = selfing; /* the first offender's value */
+				stat = 1;
+			}
+		}
+		unsigned flag = (i < d.N && stat == 1) ? 1u : 0u, tot, pre;
+		pre = block_excl_scan<BLOCK>(flag, sm, &tot);
+		if (i < d.N) {
+			uint64_t pos = keyed ? 2ull * (uint64_t)i : (uint64_t)i + running + pre;
+			isg_cursor c;
+			c.s = isg_wh_jump(d.tab, base, pos);
+			c.used = 0;
+			c.tape = nullptr;
+			int gen;
+			if (stat == 1) {
+				gen = isg_rgeom(&c, 1 - selfing);
+				if (gen < 1) gen = 1;
+				if (gen > 50) gen = 50;
+			} else if (stat == 0) gen = 1;
+			else gen = 50;
+			d.genprop[i] = gen;
+			d.uacc[i] = isg_cur_next(&c);
+		}
+		running += tot;
+	}
+	if (threadIdx.x == 0) *pos_out = (uint64_t)d.N + running;
+}
 
 /* ------------------------------------------------------------------------------------------ */
 /* k_loglik: log_ld_indv (mcmc.c:1726-1773) for a proposal/current pair or for cal_lkh          */
@@ -711,11 +758,11 @@ __global__ void __launch_bounds__(BLOCK) k_loglik_tab(DevView d)
 	}
 }
 
-template <int BLOCK, bool PAIR>
-__global__ void __launch_bounds__(BLOCK) k_loglik(DevView d)
+template <int BLOCK, bool PAIR, int KC>
+__device__ __forceinline__ void loglik_body(DevView d)
 {
 	__shared__ long long sm[(BLOCK / 64) * 3];
-	__shared__ double qsh[ISG_KCAP];
+	__shared__ double qsh[KC];
 	const int i = blockIdx.x;
 	int gp = 1, gc;
 	if (PAIR) {
@@ -797,6 +844,10 @@ __global__ void __launch_bounds__(BLOCK) k_loglik(DevView d)
 		}
 	}
 }
+template <int BLOCK, bool PAIR>
+__global__ void __launch_bounds__(BLOCK) k_loglik(DevView d) { loglik_body<BLOCK, PAIR, ISG_KCAP>(d); }
+template <int BLOCK, bool PAIR> /* K > ISG_KCAP */
+__global__ void __launch_bounds__(BLOCK) k_loglik_w(DevView d) { loglik_body<BLOCK, PAIR, ISG_KWIDE>(d); }
 
 /* ------------------------------------------------------------------------------------------ */
 /* k_zq: update_ZQ (mcmc.c:1122-1203)                                                          */
@@ -917,19 +968,27 @@ __device__ __forceinline__ double weights_reg(const double (&F)[KMAX], const dou
 	return run;
 }
 
-struct ZqShared {
+template <int KCAP>
+struct ZqSharedT {
+	static constexpr int KC = KCAP;
 	isg_wh_tables tab;          /* skip-ahead tables (2.2 KB) */
 	unsigned scan[17];
-	int hist[2][ISG_KCAP];      /* bucket counts, double buffered by individual parity (chain kernel) */
+	int hist[2][KCAP];          /* bucket counts, double buffered by individual parity (chain kernel) */
 	double at_val[1024];        /* Dirichlet attempt table: value (< 0: rejected) ... */
 	unsigned char at_used[1024];/* ... and uniforms consumed, per (gamma m, even start offset) */
-	double gval[ISG_KCAP];      /* accepted gamma values, stream order */
+	double gval[KCAP];          /* accepted gamma values, stream order */
 	unsigned long long used_total;
-	unsigned amask[2][ISG_KCAP]; /* cooperative kernel: per gamma, bit o = the attempt at even offset o is accepted ... */
-	unsigned rmask[2][ISG_KCAP]; /* ... / did NOT consume exactly two uniforms (double buffered by individual parity) */
-	int ghist[2][ISG_KCAP];      /* cooperative kernel: the other workgroups' bucket counts */
-	int hist3[3][ISG_KCAP], ghist3[3][ISG_KCAP]; /* k_zq_spec: the same, triple buffered (its Dirichlet has no barrier) */
+	unsigned amask[2][KCAP];    /* cooperative kernel: per gamma, bit o = the attempt at even offset o is accepted ... */
+	unsigned rmask[2][KCAP];    /* ... / did NOT consume exactly two uniforms (double buffered by individual parity) */
+	int ghist[2][KCAP];         /* cooperative kernel: the other workgroups' bucket counts */
+	int hist3[3][KCAP], ghist3[3][KCAP]; /* k_zq_spec: the same, triple buffered (its Dirichlet has no barrier) */
 };
+typedef ZqSharedT<ISG_KCAP> ZqShared;
+/* the wide kernels (K > ISG_KCAP) also keep the individual's qq row in LDS instead of registers */
+struct ZqSharedW : ZqSharedT<ISG_KWIDE> {
+	double qw[ISG_KWIDE];
+};
+template <int KMAX> using ZqSh = typename std::conditional<(KMAX > ISG_KCAP), ZqSharedW, ZqShared>::type;
 
 /*
  * rdirich(qqnum[i], K, &qq[i], alpha) (mcmc.c:1196-1198, random.c:264-280).  The K gammas consume the
@@ -941,7 +1000,7 @@ struct ZqShared {
  * Returns (for every thread) the number of uniforms consumed.
  */
 template <int BLOCK, int KMAX, bool WRITE = true>
-__device__ __forceinline__ unsigned dirichlet_block(const DevView &d, ZqShared &sh, int i, isg_wh dstart, double alpha, int par)
+__device__ __forceinline__ unsigned dirichlet_block(const DevView &d, ZqSh<KMAX> &sh, int i, isg_wh dstart, double alpha, int par)
 {
 	const double *dtape = nullptr; /* (the cooperative kernels read their uniforms from the tape: dirichlet_coop) */
 	const unsigned long long dstart_off = 0;
@@ -1038,7 +1097,7 @@ template <int KMAX>
 struct ZqPrefetch {
 	unsigned long long gb; /* this lane's first 8 genotype bytes */
 	int nvalid;
-	double q[KMAX];
+	double q[KMAX > ISG_KCAP ? 1 : KMAX]; /* (wide kernels: the row is staged in LDS by zq_one) */
 };
 template <int KMAX>
 __device__ __forceinline__ void zq_prefetch(const DevView &d, int i, int init_flag, ZqPrefetch<KMAX> &pf)
@@ -1050,8 +1109,10 @@ __device__ __forceinline__ void zq_prefetch(const DevView &d, int i, int init_fl
 		pf.gb = ((unsigned long long)g.y << 32) | g.x;
 	}
 	pf.nvalid = d.nvalid[i];
+	if constexpr (KMAX <= ISG_KCAP) {
 #pragma unroll
-	for (int m = 0; m < KMAX; m++) pf.q[m] = (m < d.K && !init_flag) ? d.qq[(size_t)i * d.K + m] : 0.0;
+		for (int m = 0; m < KMAX; m++) pf.q[m] = (m < d.K && !init_flag) ? d.qq[(size_t)i * d.K + m] : 0.0;
+	}
 }
 
 /*
@@ -1120,8 +1181,9 @@ __device__ __forceinline__ int bucket_f32(float xf, const float (&F)[KMAX], cons
  * from the start of the phase (index into the uniform tape).  Returns uniforms consumed. */
 /* WRITE = false: only the consumption is wanted (Z, qq, qqnum stay as they are) */
 template <int BLOCK, int KMAX, bool CHAIN, bool WRITE = true>
-__device__ __forceinline__ unsigned zq_one(const DevView &d, ZqShared &sh, int i, isg_wh cur, unsigned long long off, int init_flag,
-					   double alpha, isg_wh mult0, isg_wh mult_pass, ZqPrefetch<KMAX> &pf)
+__device__ __forceinline__ typename std::enable_if<(KMAX <= ISG_KCAP), unsigned>::type
+zq_one(const DevView &d, ZqShared &sh, int i, isg_wh cur, unsigned long long off, int init_flag, double alpha, isg_wh mult0, isg_wh mult_pass,
+       ZqPrefetch<KMAX> &pf)
 {
 	constexpr bool HOIST = (KMAX <= 8); /* float frequency rows of a pass in registers before they are used */
 	const int K = d.K, t = threadIdx.x;
@@ -1330,17 +1392,163 @@ __device__ __forceinline__ unsigned zq_one(const DevView &d, ZqShared &sh, int i
 	return 2u * (unsigned)nvalid + dirichlet_block<BLOCK, KMAX, WRITE>(d, sh, i, dstart, alpha, par);
 }
 
+/*
+ * K > ISG_KCAP (DESIGN.md §4 "K up to 64"): the same draws with no per-lane array of K entries.  The individual's qq row
+ * sits in LDS; a draw forms its running sums twice in the reference's order (mcmc.c:1146-1147) -- once for the total, once
+ * while it counts the thresholds it clears -- and repeating the same roundings in the same order gives the same bits as
+ * weights() / bucket_fast().  Every draw is decided in double, as zq_one does for K > 8: no single precision pre-filter.
+ */
+__device__ __forceinline__ int wide_bucket(double x, const double *__restrict__ F, const double *q, int K)
+{
+	double tot = 0;
+	for (int m = 0; m < K; m++) tot = (m == 0) ? q[0] * F[0] : tot + q[m] * F[m];
+	const double thr = (x * tot) * 0x1p-48;
+	bool amb = !(tot > 1e-280 && tot < 1e280);
+	int z = 0;
+	double run = 0;
+	for (int m = 0; m < K - 1; m++) {
+		run = (m == 0) ? q[0] * F[0] : run + q[m] * F[m];
+		const double dd = isg_fma(x, tot, -run);
+		z += (dd > thr) ? 1 : 0;
+		amb |= !(dd > thr || dd < -thr);
+	}
+	if (amb) { /* inside the guard band: the reference's divisions */
+		z = 0;
+		for (int m = 0; m < K - 1; m++) {
+			run = (m == 0) ? q[0] * F[0] : run + q[m] * F[m];
+			z += (run / tot < x) ? 1 : 0;
+		}
+	}
+	return z;
+}
+/* update_ZQ(init): vec[m] = (m + 1) / K, total 1 (mcmc.c:1144) */
+__device__ __forceinline__ int wide_bucket_init(double x, int K)
+{
+	const double thr = x * 0x1p-48;
+	bool amb = false;
+	int z = 0;
+	for (int m = 0; m < K - 1; m++) {
+		const double dd = isg_fma(x, 1.0, -((double)(m + 1) / K));
+		z += (dd > thr) ? 1 : 0;
+		amb |= !(dd > thr || dd < -thr);
+	}
+	if (amb) {
+		z = 0;
+		for (int m = 0; m < K - 1; m++) z += ((double)(m + 1) / K / 1.0 < x) ? 1 : 0;
+	}
+	return z;
+}
+template <int BLOCK, int KMAX, bool CHAIN, bool WRITE = true>
+__device__ __forceinline__ typename std::enable_if<(KMAX > ISG_KCAP), unsigned>::type
+zq_one(const DevView &d, ZqSharedW &sh, int i, isg_wh cur, unsigned long long off, int init_flag, double alpha, isg_wh mult0, isg_wh mult_pass,
+       ZqPrefetch<KMAX> &pf)
+{
+	const int K = d.K, t = threadIdx.x;
+	const int nvalid = pf.nvalid;
+	const bool fast = (nvalid == d.L);
+	const bool taped = CHAIN && d.tape != nullptr && off + 2ull * (unsigned)nvalid <= d.tape_len;
+	/* the qq row -> LDS.  (The previous individual's draws, the only readers, finished before its Dirichlet's barriers.) */
+	for (int m = t; m < K; m += BLOCK) sh.qw[m] = init_flag ? 0.0 : d.qq[(size_t)i * K + m];
+	unsigned long long gb = pf.gb;
+	if (CHAIN && i + 1 < d.N) zq_prefetch<KMAX>(d, i + 1, init_flag, pf);
+	__syncthreads();
+	const int par = CHAIN ? (i & 1) : 0;
+	const size_t rowb = (size_t)d.Lp * 2;
+	const uint8_t *grow = d.geno + (size_t)i * rowb;
+	uint8_t *zrow = d.z + (size_t)i * rowb;
+	unsigned running = 0;
+	isg_wh mult = mult0;
+	for (int jb = 0; jb < d.Lp; jb += BLOCK * ISG_LPT) {
+		const int j0 = jb + t * ISG_LPT;
+		unsigned long long gnext = ~0ull;
+		if (j0 + BLOCK * ISG_LPT < d.Lp) {
+			const uint2 g = *(const uint2 *)(grow + (size_t)(j0 + BLOCK * ISG_LPT) * 2);
+			gnext = ((unsigned long long)g.y << 32) | g.x;
+		}
+		unsigned nv = 0;
+#pragma unroll
+		for (int l = 0; l < ISG_LPT; l++) nv += (((unsigned)(gb >> (16 * l)) & 0xff) != 0xff) ? 1u : 0u;
+		unsigned rank;
+		if (fast) {
+			rank = (unsigned)j0;
+		} else {
+			unsigned tot;
+			rank = running + block_excl_scan<BLOCK>(nv, sh.scan, &tot);
+			running += tot;
+		}
+		double x[2 * ISG_LPT];
+		if (taped) {
+			const double *tp = d.tape + off + 2ull * rank;
+			unsigned k = 0;
+#pragma unroll
+			for (int l = 0; l < ISG_LPT; l++) {
+				const bool valid = (((unsigned)(gb >> (16 * l)) & 0xff) != 0xff);
+				x[2 * l] = valid ? tp[k] : 0.0;
+				x[2 * l + 1] = valid ? tp[k + 1] : 0.0;
+				k += valid ? 2u : 0u;
+			}
+		} else {
+			isg_wh s;
+			if (fast) {
+				s = isg_wh_mul(cur, mult);
+				mult = isg_wh_mul(mult, mult_pass);
+			} else {
+				s = isg_wh_jump32(&sh.tab, cur, 2u * rank);
+			}
+#pragma unroll
+			for (int l = 0; l < ISG_LPT; l++) {
+				const bool valid = (((unsigned)(gb >> (16 * l)) & 0xff) != 0xff);
+				isg_wh s2 = s;
+#pragma unroll
+				for (int cp = 0; cp < 2; cp++) {
+					isg_wh_step(&s2);
+					x[2 * l + cp] = isg_wh_value(&s2);
+				}
+				s.s1 = valid ? s2.s1 : s.s1; /* unused loci consume nothing (mcmc.c:1137) */
+				s.s2 = valid ? s2.s2 : s.s2;
+				s.s3 = valid ? s2.s3 : s.s3;
+			}
+		}
+		unsigned long long zb = ~0ull;
+		for (int l = 0; l < ISG_LPT; l++) {
+			const unsigned a0 = (unsigned)(gb >> (16 * l)) & 0xff, a1 = (unsigned)(gb >> (16 * l + 8)) & 0xff;
+			if (a0 == 0xff) continue;
+			int z0, z1;
+			if (init_flag) {
+				z0 = wide_bucket_init(x[2 * l], K);
+				z1 = wide_bucket_init(x[2 * l + 1], K);
+			} else {
+				z0 = wide_bucket(x[2 * l], d.freq + ((size_t)(j0 + l) * d.Amax + a0) * d.KP, sh.qw, K);
+				z1 = wide_bucket(x[2 * l + 1], d.freq + ((size_t)(j0 + l) * d.Amax + a1) * d.KP, sh.qw, K);
+			}
+			atomicAdd(&sh.hist[par][z0], 1); /* qqnum[i][m] (mcmc.c:1176-1194) */
+			atomicAdd(&sh.hist[par][z1], 1);
+			zb = (zb & ~(0xffffull << (16 * l))) | ((unsigned long long)(z0 | (z1 << 8)) << (16 * l));
+		}
+		if (WRITE && j0 < d.Lp) {
+			uint2 zo;
+			zo.x = (unsigned)zb;
+			zo.y = (unsigned)(zb >> 32);
+			*(uint2 *)(zrow + (size_t)j0 * 2) = zo;
+		}
+		gb = gnext;
+	}
+	lds_barrier();
+	const isg_wh dstart = isg_wh_jump32(&sh.tab, cur, 2u * (unsigned)nvalid);
+	return 2u * (unsigned)nvalid + dirichlet_block<BLOCK, KMAX, WRITE>(d, sh, i, dstart, alpha, par);
+}
+
 template <int BLOCK, int KMAX, bool CHAIN>
 __global__ void __launch_bounds__(BLOCK) k_zq(DevView d, isg_wh base, uint64_t pos0, uint64_t stride, int init_flag, double alpha,
 					      uint64_t *pos_out)
 {
-	__shared__ ZqShared sh;
+	__shared__ ZqSh<KMAX> sh;
 	const int t = threadIdx.x;
 	{ /* skip-ahead tables -> LDS */
 		const uint16_t *src = (const uint16_t *)d.tab;
 		uint16_t *dst = (uint16_t *)&sh.tab;
 		for (int k = t; k < (int)(sizeof(isg_wh_tables) / 2); k += BLOCK) dst[k] = src[k];
-		if (t < 2 * ISG_KCAP) (&sh.hist[0][0])[t] = 0;
+		if (t < 2 * ZqSh<KMAX>::KC) (&sh.hist[0][0])[t] = 0;
 	}
 	__syncthreads();
 	/* multipliers for lane t: its first copy sits 2*4*t uniforms into a pass, a pass spans 8*BLOCK */
@@ -2652,12 +2860,12 @@ __device__ __forceinline__ double dev_proposal(const DevView &d, const double *s
 	const isg_acc r = block_reduce_acc<BLOCK>(a, smr);
 	return isg_acc_value(&r);
 }
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_spop(DevView d, double *S, int *state, isg_wh start, int back_refl, uint64_t *used_out)
+template <int BLOCK, int KC>
+__device__ __forceinline__ void spop_body(DevView d, double *S, int *state, isg_wh start, int back_refl, uint64_t *used_out)
 {
 	__shared__ unsigned long long smr[(BLOCK / 64) * 5];
-	__shared__ double Scur[ISG_KCAP], Stmp[ISG_KCAP];
-	__shared__ int stc[ISG_KCAP], stt[ISG_KCAP];
+	__shared__ double Scur[KC], Stmp[KC];
+	__shared__ int stc[KC], stt[KC];
 	__shared__ double ld_sh;
 	const int t = threadIdx.x, K = d.K;
 	if (t < K) { Scur[t] = S[t]; stc[t] = state[t]; }
@@ -2719,6 +2927,10 @@ __global__ void __launch_bounds__(BLOCK) k_spop(DevView d, double *S, int *state
 	if (t < K) { S[t] = Scur[t]; state[t] = stc[t]; }
 	if (t == 0) *used_out = c.used;
 }
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_spop(DevView d, double *S, int *state, isg_wh start, int back_refl, uint64_t *used_out) { spop_body<BLOCK, ISG_KCAP>(d, S, state, start, back_refl, used_out); }
+template <int BLOCK> /* K > ISG_KCAP */
+__global__ void __launch_bounds__(BLOCK) k_spop_w(DevView d, double *S, int *state, isg_wh start, int back_refl, uint64_t *used_out) { spop_body<BLOCK, ISG_KWIDE>(d, S, state, start, back_refl, used_out); }
 
 /*
  * update_S_POP for -e 1 and K <= 6, spread over the chip.  The proposal of step j is a reflected +-0.05 step from the
@@ -3184,7 +3396,7 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	*out = nullptr;
 	if (cfg->P == 4) return fail("isg_ctx_create: ploidy 4 data goes through isg_ctx_create_poly");
 	if (cfg->P != 2) return fail("isg_ctx_create: only ploidy 2 and 4 are supported");
-	if (cfg->K < 1 || cfg->K > ISG_KCAP) return fail("isg_ctx_create: K must be in 1..32");
+	if (cfg->K < 1 || cfg->K > ISG_KWIDE) return fail("isg_ctx_create: K must be in 1..64 for ploidy 2");
 	if (cfg->mode < 0 || cfg->mode > 5) return fail("isg_ctx_create: mode must be 0 .. 5");
 	if (cfg->N < 1 || cfg->L < 1) return fail("isg_ctx_create: empty problem");
 	int ndev = 0;
@@ -3322,10 +3534,10 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	d.tab = dt;
 	DALLOC(c->d_pos, uint64_t, 4);
 	DALLOC(c->d_err, unsigned, 4);
-	DALLOC(c->d_S, double, ((cfg->mode == 3 || cfg->mode == 5) && N > ISG_KCAP) ? N : ISG_KCAP); /* modes 3, 5: one value per individual */
+	DALLOC(c->d_S, double, ((cfg->mode == 3 || cfg->mode == 5) && N > ISG_KWIDE) ? N : ISG_KWIDE); /* modes 3, 5: one value per individual */
 	c->d_Fprop = nullptr;
 	if (cfg->mode == 5) { DALLOC(c->d_Fprop, double, N); }
-	DALLOC(c->d_state, int, ISG_KCAP);
+	DALLOC(c->d_state, int, ISG_KWIDE);
 	DALLOC(c->d_ratios, double, (size_t)N * K);
 	DALLOC(c->d_total, double, 1);
 	c->ratios_h.assign((size_t)N * K, 0.0);
@@ -3686,7 +3898,8 @@ extern "C" int isg_update_S_POP(isg_ctx *c)
 		prof_end(c, "k_spop");
 	} else {
 		prof_begin(c);
-		hipLaunchKernelGGL(k_spop<1024>, dim3(1), dim3(1024), 0, c->stream, c->d, c->d_S, c->d_state, start, c->cfg.back_refl, c->d_pos + 1);
+		if (K > ISG_KCAP) hipLaunchKernelGGL(k_spop_w<1024>, dim3(1), dim3(1024), 0, c->stream, c->d, c->d_S, c->d_state, start, c->cfg.back_refl, c->d_pos + 1);
+		else hipLaunchKernelGGL(k_spop<1024>, dim3(1), dim3(1024), 0, c->stream, c->d, c->d_S, c->d_state, start, c->cfg.back_refl, c->d_pos + 1);
 		prof_end(c, "k_spop");
 	}
 	HIPCHK(hipGetLastError());
@@ -3712,11 +3925,13 @@ extern "C" int isg_update_G(isg_ctx *c)
 	double *d_S = c->d_S;
 	isg_wh base = is_keyed(c) ? isg_wh_jump(&c->tab_h, c->origin, iter_base(c) + c->ky[KY_OFFG]) : c->rng;
 	prof_begin(c);
-	hipLaunchKernelGGL(k_gprop<1024>, dim3(1), dim3(1024), 0, c->stream, d, (const double *)d_S, base, is_keyed(c) ? 1 : 0, c->d_pos);
+	if (d.K > ISG_KCAP) hipLaunchKernelGGL(k_gprop_w<1024>, dim3(1), dim3(1024), 0, c->stream, d, (const double *)d_S, base, is_keyed(c) ? 1 : 0, c->d_pos);
+	else hipLaunchKernelGGL(k_gprop<1024>, dim3(1), dim3(1024), 0, c->stream, d, (const double *)d_S, base, is_keyed(c) ? 1 : 0, c->d_pos);
 	prof_end(c, "k_gprop");
 	prof_begin(c);
 	if (d.lli && d.mode == 2) hipLaunchKernelGGL((k_loglik_int<256, true>), dim3(d.N), dim3(256), 0, c->stream, d);
 	else if (d.lltab) hipLaunchKernelGGL((k_loglik_tab<256, true>), dim3(d.N), dim3(256), 0, c->stream, d);
+	else if (d.K > ISG_KCAP) hipLaunchKernelGGL((k_loglik_w<256, true>), dim3(d.N), dim3(256), 0, c->stream, d);
 	else hipLaunchKernelGGL((k_loglik<256, true>), dim3(d.N), dim3(256), 0, c->stream, d);
 	prof_end(c, "k_loglik_pair");
 	HIPCHK(hipGetLastError());
@@ -3795,7 +4010,7 @@ extern "C" int isg_update_ZQ(isg_ctx *c, int init_flag)
 		c->d.tape = c->d_tape;
 		c->d.tape_len = need;
 	}
-	const bool coop = chain && c->coop;
+	const bool coop = chain && c->coop && K <= ISG_KCAP; /* K > ISG_KCAP: the chain form of the wide k_zq */
 	if (coop) {
 		HIPCHK(hipMemsetAsync(c->d_coop, 0, sizeof(CoopBuf), c->stream));
 		int G = (c->d.Lp + 255) / 256;
@@ -3886,7 +4101,8 @@ extern "C" int isg_update_ZQ(isg_ctx *c, int init_flag)
 		if (K <= 12) launch_zq<12>(c, chain, base, pos0, stride, init_flag);
 		else if (K <= 16) launch_zq<16>(c, chain, base, pos0, stride, init_flag);
 		else if (K <= 24) launch_zq<24>(c, chain, base, pos0, stride, init_flag);
-		else launch_zq<32>(c, chain, base, pos0, stride, init_flag);
+		else if (K <= ISG_KCAP) launch_zq<32>(c, chain, base, pos0, stride, init_flag);
+		else launch_zq<ISG_KWIDE>(c, chain, base, pos0, stride, init_flag); /* K-generic wide kernels (zq_one, K > ISG_KCAP) */
 	}
 	prof_end(c, chain ? "k_zq_chain" : "k_zq_keyed");
 	HIPCHK(hipGetLastError());
@@ -3941,6 +4157,7 @@ extern "C" int isg_cal_lkh(isg_ctx *c)
 	prof_begin(c);
 	if (d.lli && d.mode == 2) hipLaunchKernelGGL((k_loglik_int<256, false>), dim3(d.N), dim3(256), 0, c->stream, d);
 	else if (d.lltab || (d.lftab && d.mode == 1)) hipLaunchKernelGGL((k_loglik_tab<256, false>), dim3(d.N), dim3(256), 0, c->stream, d);
+	else if (d.K > ISG_KCAP) hipLaunchKernelGGL((k_loglik_w<256, false>), dim3(d.N), dim3(256), 0, c->stream, d);
 	else hipLaunchKernelGGL((k_loglik<256, false>), dim3(d.N), dim3(256), 0, c->stream, d);
 	prof_end(c, "k_loglik_lkh");
 	prof_begin(c);

@@ -84,7 +84,8 @@ __global__ void __launch_bounds__(256) k_paircount(DevView d, int chunk, int *np
 
 /* blockIdx.y = accumulator slot: 0 sum cntmix log freq; 1 + k / 1 + K + k the pair terms of cluster k at the current /
  * proposed coefficient.  One block reduction, one set of atomics per block. */
-__global__ void __launch_bounds__(256) k_Fsums(DevView d, const int *npair, const int *cntmix, const double *F, unsigned long long *acc)
+template <int FS> /* F: [2][FS], current and proposed coefficients */
+__device__ __forceinline__ void Fsums_body(DevView d, const int *npair, const int *cntmix, const double *F, unsigned long long *acc)
 {
 	__shared__ unsigned long long sm[4 * 5];
 	const int A = d.Amax, K = d.K, slot = blockIdx.y;
@@ -105,12 +106,15 @@ __global__ void __launch_bounds__(256) k_Fsums(DevView d, const int *npair, cons
 		if (c) {
 			const int a1 = (int)(id % A), a0 = (int)((id / A) % A), j = (int)(id / A / A);
 			const double f0 = d.freq[((size_t)j * A + a0) * d.KP + k], f1 = d.freq[((size_t)j * A + a1) * d.KP + k];
-			acc_add_times(&a, isg_log(genofreq_F(a0 == a1, f0, f1, F[prop * ISG_KCAP + k])), c);
+			acc_add_times(&a, isg_log(genofreq_F(a0 == a1, f0, f1, F[prop * FS + k])), c);
 		}
 	}
 	const isg_acc r = block_reduce_acc<256>(a, sm);
 	if (threadIdx.x == 0) acc_global_add(acc + 5 * slot, r);
 }
+__global__ void __launch_bounds__(256) k_Fsums(DevView d, const int *npair, const int *cntmix, const double *F, unsigned long long *acc) { Fsums_body<ISG_KCAP>(d, npair, cntmix, F, acc); }
+/* K > ISG_KCAP */
+__global__ void __launch_bounds__(256) k_Fsums_w(DevView d, const int *npair, const int *cntmix, const double *F, unsigned long long *acc) { Fsums_body<ISG_KWIDE>(d, npair, cntmix, F, acc); }
 
 /* lltab slot 0 = log genofreq_F(f0, f1, F_k): cal_lkh's same-cluster terms (k_loglik_tab reads it with generation 1) */
 __global__ void k_lltabF(DevView d, const double *F)
@@ -137,8 +141,8 @@ static int inbreed_alloc(isg_ctx *c)
 	IALLOC(ib->d_npair, int, (size_t)L * A * A * K);
 	IALLOC(ib->d_cntmix, int, (size_t)L * A * K);
 	IALLOC(ib->d_nhet, unsigned long long, 1);
-	IALLOC(ib->d_acc, unsigned long long, 5 * (2 * ISG_KCAP + 2));
-	IALLOC(ib->d_F, double, 2 * ISG_KCAP);
+	IALLOC(ib->d_acc, unsigned long long, 5 * (2 * ISG_KWIDE + 2));
+	IALLOC(ib->d_F, double, 2 * ISG_KWIDE);
 #undef IALLOC
 	return 0;
 }
@@ -190,18 +194,23 @@ static int inbreed_update_F_POP(isg_ctx *c) /* update_inbreedcoff_POP, mcmc.c:98
 		prop[j] = tmp;
 		uacc[j] = host_next(c);
 	}
-	double Fs[2 * ISG_KCAP];
+	const int FS = (K > ISG_KCAP) ? ISG_KWIDE : ISG_KCAP; /* k_Fsums / k_Fsums_w: [2][FS] */
+	double Fs[2 * ISG_KWIDE];
 	for (int k = 0; k < K; k++) {
 		Fs[k] = c->S[k];
-		Fs[ISG_KCAP + k] = prop[k];
+		Fs[FS + k] = prop[k];
 	}
-	HIPCHK(hipMemcpyAsync(ib->d_F, Fs, sizeof(Fs), hipMemcpyHostToDevice, c->stream));
-	HIPCHK(hipMemsetAsync(ib->d_acc, 0, sizeof(unsigned long long) * 5 * (2 * ISG_KCAP + 2), c->stream));
+	HIPCHK(hipMemcpyAsync(ib->d_F, Fs, sizeof(double) * 2 * FS, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemsetAsync(ib->d_acc, 0, sizeof(unsigned long long) * 5 * (2 * FS + 2), c->stream));
 	{
 		const size_t ne = (size_t)L * A * (A > K ? A : K);
 		prof_begin(c);
-		hipLaunchKernelGGL(k_Fsums, dim3((unsigned)((ne + 255) / 256), 2 * K + 1), dim3(256), 0, c->stream, d, (const int *)ib->d_npair, (const int *)ib->d_cntmix,
-				   (const double *)ib->d_F, ib->d_acc);
+		if (K > ISG_KCAP)
+			hipLaunchKernelGGL(k_Fsums_w, dim3((unsigned)((ne + 255) / 256), 2 * K + 1), dim3(256), 0, c->stream, d, (const int *)ib->d_npair, (const int *)ib->d_cntmix,
+					   (const double *)ib->d_F, ib->d_acc);
+		else
+			hipLaunchKernelGGL(k_Fsums, dim3((unsigned)((ne + 255) / 256), 2 * K + 1), dim3(256), 0, c->stream, d, (const int *)ib->d_npair, (const int *)ib->d_cntmix,
+					   (const double *)ib->d_F, ib->d_acc);
 		prof_end(c, "k_Fsums");
 	}
 	HIPCHK(hipGetLastError());
@@ -408,11 +417,11 @@ static int indiv_cal_lkh_F(isg_ctx *c)
 /* zz[i] is kept in gen[i] (this mode has no generations) and mirrored into the individual's z bytes so that       */
 /* update_P's allele counts (mcmc.c:825-829) are k_count's.  what: 0 initial draw, 1 update, 2 log-likelihood only. */
 /* ------------------------------------------------------------------------------------------ */
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_z0(DevView d, isg_wh base, unsigned long long stride, int what)
+template <int BLOCK, int KC>
+__device__ __forceinline__ void z0_body(DevView d, isg_wh base, unsigned long long stride, int what)
 {
 	__shared__ long long sm[(BLOCK / 64) * 3];
-	__shared__ double ld[ISG_KCAP];
+	__shared__ double ld[KC];
 	__shared__ int zsh;
 	const int i = blockIdx.x, K = d.K, t = threadIdx.x;
 	const size_t rowb = (size_t)d.Lp * 2;
@@ -439,7 +448,7 @@ __global__ void __launch_bounds__(BLOCK) k_z0(DevView d, isg_wh base, unsigned l
 	if (t == 0) {
 		int zz = d.gen[i];
 		if (what != 2) {
-			double cum[ISG_KCAP];
+			double cum[KC];
 			for (int m = 0; m < K; m++) {
 				if (what == 0) cum[m] = (double)(m + 1) / K;
 				else {
@@ -461,6 +470,10 @@ __global__ void __launch_bounds__(BLOCK) k_z0(DevView d, isg_wh base, unsigned l
 			if (grow[(size_t)j * 2] != 0xff) *(unsigned short *)(d.z + (size_t)i * rowb + (size_t)j * 2) = zw;
 	}
 }
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_z0(DevView d, isg_wh base, unsigned long long stride, int what) { z0_body<BLOCK, ISG_KCAP>(d, base, stride, what); }
+template <int BLOCK> /* K > ISG_KCAP */
+__global__ void __launch_bounds__(BLOCK) k_z0_w(DevView d, isg_wh base, unsigned long long stride, int what) { z0_body<BLOCK, ISG_KWIDE>(d, base, stride, what); }
 
 static int noadm_update_Z(isg_ctx *c, int init_flag)
 {
@@ -475,7 +488,8 @@ static int noadm_update_Z(isg_ctx *c, int init_flag)
 		stride = 1;
 	}
 	prof_begin(c);
-	hipLaunchKernelGGL(k_z0<256>, dim3(N), dim3(256), 0, c->stream, c->d, base, stride, init_flag ? 0 : 1);
+	if (c->cfg.K > ISG_KCAP) hipLaunchKernelGGL(k_z0_w<256>, dim3(N), dim3(256), 0, c->stream, c->d, base, stride, init_flag ? 0 : 1);
+	else hipLaunchKernelGGL(k_z0<256>, dim3(N), dim3(256), 0, c->stream, c->d, base, stride, init_flag ? 0 : 1);
 	prof_end(c, "k_z0");
 	HIPCHK(hipGetLastError());
 	if (!is_keyed(c)) host_advance(c, (uint64_t)N);
@@ -487,7 +501,8 @@ static int noadm_update_Z(isg_ctx *c, int init_flag)
 static int noadm_cal_lkh(isg_ctx *c)
 {
 	prof_begin(c);
-	hipLaunchKernelGGL(k_z0<256>, dim3(c->cfg.N), dim3(256), 0, c->stream, c->d, c->rng, 0ull, 2);
+	if (c->cfg.K > ISG_KCAP) hipLaunchKernelGGL(k_z0_w<256>, dim3(c->cfg.N), dim3(256), 0, c->stream, c->d, c->rng, 0ull, 2);
+	else hipLaunchKernelGGL(k_z0<256>, dim3(c->cfg.N), dim3(256), 0, c->stream, c->d, c->rng, 0ull, 2);
 	prof_end(c, "k_z0_lkh");
 	prof_begin(c);
 	hipLaunchKernelGGL(k_lkh_total<1024>, dim3(1), dim3(1024), 0, c->stream, c->d, c->d_total);

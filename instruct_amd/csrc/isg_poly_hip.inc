@@ -1205,7 +1205,7 @@ __global__ void k4_pdirich(PolyDev p, isg_wh base, uint64_t pos0, uint64_t SP)
 /* ------------------------------------------------------------------------------------------ */
 static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, const int32_t *seq, isg_ctx **out)
 {
-	if (cfg->K < 1 || cfg->K > ISG_KCAP) return fail("isg_ctx_create: K must be in 1..32");
+	if (cfg->K < 1 || cfg->K > ISG_KCAP) return fail("isg_ctx_create_poly: K must be in 1..32 for ploidy 4");
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("isg_ctx_create: no HIP device available (the MI355X path has no CPU fallback)");
 	if (cfg->device < 0 || cfg->device >= ndev) return fail("isg_ctx_create: bad device ordinal");

@@ -641,14 +641,14 @@ __global__ void __launch_bounds__(256, ISG_RS_OCC) k_zq_blocks(DevView d, isg_wh
 template <int BLOCK, int KMAX>
 __global__ void __launch_bounds__(BLOCK) k_zq_at(DevView d, isg_wh base, double alpha, const ResolveState *st, const unsigned long long *offs)
 {
-	__shared__ ZqShared sh;
+	__shared__ ZqSh<KMAX> sh;
 	if (!st->done || st->fail) return;
 	const int t = threadIdx.x, i = blockIdx.x;
 	{
 		const uint16_t *src = (const uint16_t *)d.tab;
 		uint16_t *dst = (uint16_t *)&sh.tab;
 		for (int k = t; k < (int)(sizeof(isg_wh_tables) / 2); k += BLOCK) dst[k] = src[k];
-		if (t < 2 * ISG_KCAP) (&sh.hist[0][0])[t] = 0;
+		if (t < 2 * ZqSh<KMAX>::KC) (&sh.hist[0][0])[t] = 0;
 	}
 	__syncthreads();
 	const isg_wh mult0 = isg_wh_power(&sh.tab, 8u * (unsigned)t);

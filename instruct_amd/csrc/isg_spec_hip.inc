@@ -201,12 +201,75 @@ __global__ void __launch_bounds__(256) k_zs_band(const WkBlock *blk, const WkSeg
 	}
 }
 
+/* K > ISG_KCAP: the same intervals, one workgroup per (individual, ISG_ZX_WCH clusters).  Each copy's total is formed anew from the qq
+ * row in LDS (K terms) so that a lane holds ISG_ZX_WCH accumulator pairs whatever K is. */
+#define ISG_ZX_WCH 16
+__global__ void __launch_bounds__(256) k_zexpect_w(DevView d, double alpha, float ksig, float *alo, float *ahi)
+{
+	__shared__ float qs[ISG_KWIDE];
+	__shared__ float red[4][2 * ISG_ZX_WCH];
+	const int i = blockIdx.x, k0 = blockIdx.y * ISG_ZX_WCH, t = threadIdx.x, K = d.K, lane = (int)lane_id();
+	if (t < K) qs[t] = (float)d.qq[(size_t)i * K + t];
+	__syncthreads();
+	float lam[ISG_ZX_WCH], var[ISG_ZX_WCH];
+#pragma unroll
+	for (int h = 0; h < ISG_ZX_WCH; h++) lam[h] = var[h] = 0.f;
+	const unsigned short *grow = (const unsigned short *)(d.geno + (size_t)i * d.Lp * 2);
+	for (int j = t; j < d.Lp; j += 256) {
+		const unsigned g = grow[j];
+		const unsigned a0 = g & 0xff, a1 = g >> 8;
+		if (a0 == 0xff) continue;
+		for (int cp = 0; cp < 2; cp++) {
+			const float *F = d.freqf + ((size_t)j * d.Amax + (cp ? a1 : a0)) * d.KPF;
+			float tot = 0.f;
+			for (int m = 0; m < K; m++) tot += qs[m] * F[m];
+			const float inv = (tot > 0.f) ? 1.0f / tot : 0.f;
+#pragma unroll
+			for (int h = 0; h < ISG_ZX_WCH; h++) {
+				const bool in = (k0 + h < K);
+				const int k = in ? k0 + h : 0;
+				const float pr = in ? qs[k] * F[k] * inv : 0.f;
+				lam[h] += pr;
+				var[h] += pr * (1.0f - pr);
+			}
+		}
+	}
+#pragma unroll
+	for (int h = 0; h < ISG_ZX_WCH; h++) {
+		float l = lam[h], v = var[h];
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) {
+			l += __shfl_down(l, o, 64);
+			v += __shfl_down(v, o, 64);
+		}
+		if (lane == 0) {
+			red[t >> 6][h] = l;
+			red[t >> 6][ISG_ZX_WCH + h] = v;
+		}
+	}
+	__syncthreads();
+	const int k = k0 + t;
+	if (t < ISG_ZX_WCH && k < K) { /* as k_zexpect */
+		const float l = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+		float v = red[0][ISG_ZX_WCH + t] + red[1][ISG_ZX_WCH + t] + red[2][ISG_ZX_WCH + t] + red[3][ISG_ZX_WCH + t];
+		v = v > 0.f ? v : 0.f;
+		const float h = ksig * __builtin_sqrtf(v) + 1.0f + 1e-5f * l;
+		float lo = __builtin_floorf(l - h), hi = __builtin_ceilf(l + h);
+		const float tot = 2.0f * (float)d.nvalid[i];
+		if (lo < 0.f) lo = 0.f;
+		if (hi > tot) hi = tot;
+		if (d.nvalid[i] == 0) lo = hi = 0.f;
+		alo[(size_t)i * K + k] = (float)((double)lo + alpha);
+		ahi[(size_t)i * K + k] = (float)((double)hi + alpha);
+	}
+}
+
 /* a probe: individual i started at B[i] + 2 x -- its Z draws, counts and the Dirichlet's consumption, exactly as the sweep takes them
  * (zq_one), nothing written but the table byte.  Workgroups take probes in turn. */
 template <int BLOCK, int KMAX>
 __global__ void __launch_bounds__(BLOCK) k_zq_probe(DevView d, isg_wh base, double alpha, const unsigned long long *Bpre, const SpecProbe *list, SpecDev *dev, int cap, unsigned char *table)
 {
-	__shared__ ZqShared sh;
+	__shared__ ZqSh<KMAX> sh;
 	const int t = threadIdx.x;
 	{
 		const uint16_t *src = (const uint16_t *)d.tab;
@@ -219,7 +282,7 @@ __global__ void __launch_bounds__(BLOCK) k_zq_probe(DevView d, isg_wh base, doub
 	const unsigned n = dev->nlist < (unsigned)cap ? dev->nlist : (unsigned)cap;
 	if (blockIdx.x == 0 && t == 0 && n) { dev->nprobes += n; dev->rounds += 1u; }
 	for (unsigned p = blockIdx.x; p < n; p += gridDim.x) {
-		if (t < 2 * ISG_KCAP) (&sh.hist[0][0])[t] = 0;
+		if (t < 2 * ZqSh<KMAX>::KC) (&sh.hist[0][0])[t] = 0;
 		__syncthreads();
 		const int i = list[p].i;
 		const unsigned long long o = Bpre[i] + 2ull * list[p].x;
@@ -322,7 +385,8 @@ static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid
 		if (K <= 12) CALL(12);         \
 		else if (K <= 16) CALL(16);    \
 		else if (K <= 24) CALL(24);    \
-		else CALL(32);                 \
+		else if (K <= ISG_KCAP) CALL(32); \
+		else CALL(ISG_KWIDE);          \
 	}
 
 /* launch_expect(alo, ahi) / launch_probe(grid) / launch_at(): the ploidy's kernels.  *done = false: nothing is changed (qq restored),
@@ -449,8 +513,12 @@ static int spec_update_ZQ_with(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 template <int KMAX>
 static void spec_launch_expect(isg_ctx *c, SpecCtx *sp, float *alo, float *ahi)
 {
-	constexpr int MI = KMAX <= 8 ? 4 : KMAX <= 16 ? 2 : 1; /* individuals per workgroup: 2 MI KMAX accumulators + MI KMAX weights per lane */
-	hipLaunchKernelGGL((k_zexpect<KMAX, MI>), dim3((unsigned)((c->cfg.N + MI - 1) / MI)), dim3(256), 0, c->stream, c->d, c->alpha, sp->ksig, alo, ahi);
+	if constexpr (KMAX > ISG_KCAP) {
+		hipLaunchKernelGGL(k_zexpect_w, dim3((unsigned)c->cfg.N, (unsigned)((c->cfg.K + ISG_ZX_WCH - 1) / ISG_ZX_WCH)), dim3(256), 0, c->stream, c->d, c->alpha, sp->ksig, alo, ahi);
+	} else {
+		constexpr int MI = KMAX <= 8 ? 4 : KMAX <= 16 ? 2 : 1; /* individuals per workgroup: 2 MI KMAX accumulators + MI KMAX weights per lane */
+		hipLaunchKernelGGL((k_zexpect<KMAX, MI>), dim3((unsigned)((c->cfg.N + MI - 1) / MI)), dim3(256), 0, c->stream, c->d, c->alpha, sp->ksig, alo, ahi);
+	}
 }
 template <int KMAX>
 static void spec_launch_probe(isg_ctx *c, SpecCtx *sp, isg_wh base, int grid)
