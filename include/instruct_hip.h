@@ -123,7 +123,10 @@ int isg_keyed_layout(isg_ctx *ctx, uint64_t out[9]);
  * Ploidy 4 (autotetraploid, `-p 4 -ap 1`): the chain of poly_geno.c:85-116 (mcmc_POP_tetra_selfing).
  * seqdata int32 [N][L][4]: the sorted distinct allele codes observed for (individual, locus) in the first
  * alleleid[i][j] entries (SEQDATA.seqdata / SEQDATA.alleleid as transform_data2 leaves them,
- * data_interface.c:571-669; alleleid 0 = missing).  cfg.P = 4; both schedules.  Keyed layout for ploidy 4
+ * data_interface.c:571-669; alleleid 0 = missing).  cfg.P = 4; both schedules.  Up to 32 alleles per locus in both
+ * tetraploid variants (a context whose largest allele count is 17..32 runs the wide-allele table kernels for all its loci; its five
+ * genotype tables, 4 bytes x K x L x the largest locus' genotype count each, must fit in half of the free device memory,
+ * otherwise isg_ctx_create_poly fails naming their size).  Keyed layout for ploidy 4
  * (amb = number of (individual, locus) pairs with 2 or 3 distinct alleles -- allotetraploid: 2, 3 or 4 --, rank = their order i-major):
  *   0 alpha | 1 + rank  initial_geno | ZI0 = 1 + amb, ZQ(init) of i at ZI0 + i SZ, SZ = 4 L + 16 K + 16
  *   B = B0 + t BLK, B0 = ZI0 + N SZ:  B + (k L + j) SP  update_P_auto (SP = 16 Amax + 16; allotetraploid: both subgenomes' Dirichlets, SP = 32 Amax + 32) | B + offS  update_S_POP

@@ -24,6 +24,7 @@
 #undef PT_EXP
 
 #define ISG_POLY_ACAP 16 /* alleles per locus: 3876 (auto) / 18496 (allo) genotypes at 16; rows are found through a code -> row map of n^4 shorts */
+#define ISG_POLY_ACAP_W 32 /* wide-allele contexts (Amax 17..32): 52360 (auto) / 278784 (allo) genotypes at 32, rows in closed form, own table kernels */
 
 struct PolyDev {
 	int N, L, Lp, K, KP, Amax, GS, nwv;
@@ -75,6 +76,7 @@ struct PolyCtx {
 	unsigned long long *d_catcnt;
 	bool counts_valid; /* cnt / cntmix / ccnt / catcnt describe the current (geno, Z) */
 	bool freq_host;    /* the host mirror of freq is current (replay: drawn on the host) */
+	bool wide;         /* Amax 17..32: closed-form rows (no gidmap), k4_exfreq_w / k4_genfreq_w and the *_w sweeps */
 	float *d_zpart = nullptr; /* k4_zexpect: [N][8][2 K] partial sums */
 	hvec<double> freq2_h; /* [K][L][Amax] second subgenome (allo) */
 	hvec<int> cnt2_h;
@@ -111,6 +113,13 @@ __device__ __forceinline__ int poly_gid(const PolyDev &p, int j, unsigned g0, un
 {
 	const int cl = p.lclass[j], n = p.pc[cl].n;
 	return p.gidmap[p.gidoff[cl] + (int)(((g0 * n + g1) * n + g2) * n + g3)];
+}
+/* the same row in a wide-allele context (more than 16 alleles at some locus): closed form instead of the map */
+template <bool ALLO>
+__device__ __forceinline__ int poly_row_w(const PolyDev &p, int j, unsigned g0, unsigned g1, unsigned g2, unsigned g3)
+{
+	const int n = p.pc[p.lclass[j]].n;
+	return ALLO ? isg_allo_row(n, (int)g0, (int)g1, (int)g2, (int)g3) : isg_poly_rank(n, (int)g0, (int)g1, (int)g2, (int)g3);
 }
 /* category from the table row (rows are grouped by class): 0 iiii 1 iiij 2 iijj 3 iijk 4 ijkl */
 __device__ __forceinline__ int poly_cat(const PolyDev &p, int j, int gid)
@@ -236,7 +245,7 @@ __device__ __forceinline__ void poly_set(unsigned num, int naid, const unsigned 
 }
 
 /* initial_geno (poly_geno.c:316-369, uniform choice) and update_geno (:520-580, choose_two/tri_auto :854-960) */
-template <int KMAX>
+template <int KMAX, bool WIDE>
 __device__ __forceinline__ void geno_one(const PolyDev &p, const isg_wh &base, int init, const double *tape, int i, int j, const float (&qf)[KMAX])
 {
 	const size_t id = (size_t)i * p.Lp + j;
@@ -282,6 +291,11 @@ __device__ __forceinline__ void geno_one(const PolyDev &p, const isg_wh &base, i
 					num[1] = o[1] * n * n * (n + 1) + o[0] * n + o[2];
 					num[2] = o[2] * n * n * (n + 1) + o[0] * n + o[1];
 				}
+				if (WIDE) { /* the same three genotypes, rows in closed form */
+					num[0] = naid == 2 ? isg_poly_rank(n, o[0], o[0], o[0], o[1]) : isg_poly_rank(n, o[0], o[0], o[1], o[2]);
+					num[1] = naid == 2 ? isg_poly_rank(n, o[1], o[1], o[1], o[0]) : isg_poly_rank(n, o[1], o[1], o[0], o[2]);
+					num[2] = naid == 2 ? isg_poly_rank(n, o[0], o[0], o[1], o[1]) : isg_poly_rank(n, o[2], o[2], o[0], o[1]);
+				} else
 				for (int a = 0; a < 3; a++) num[a] = p.gidmap[p.gidoff[p.lclass[j]] + num[a]];
 			}
 			/*
@@ -387,7 +401,22 @@ __global__ void __launch_bounds__(256) k4_geno(PolyDev p, isg_wh base, int init,
 #pragma unroll
 		for (int m = 0; m < KMAX; m++) qf[m] = (m < p.K && !init) ? (float)p.qq[(size_t)i * p.K + m] : 0.f;
 		if (ALLO) geno_one_allo(p, base, init, tape, i, j);
-		else geno_one<KMAX>(p, base, init, tape, i, j, qf);
+		else geno_one<KMAX, false>(p, base, init, tape, i, j, qf);
+	}
+}
+/* the autotetraploid draw of a wide-allele context (the allotetraploid draw has closed-form rows already: k4_geno<KMAX, true>) */
+template <int KMAX>
+__global__ void __launch_bounds__(256) k4_geno_w(PolyDev p, isg_wh base, int init, const double *tape, int chunk, int nchunk)
+{
+	const int b = (int)blockIdx.x, r = b >> 3;
+	const int tile = (r / nchunk) * 8 + (b & 7), ch = r % nchunk;
+	const int j = tile * 256 + (int)threadIdx.x, i0 = ch * chunk, i1 = min(p.N, i0 + chunk);
+	if (tile * 256 >= p.Lp) return;
+	for (int i = i0; i < i1; i++) {
+		float qf[KMAX];
+#pragma unroll
+		for (int m = 0; m < KMAX; m++) qf[m] = (m < p.K && !init) ? (float)p.qq[(size_t)i * p.K + m] : 0.f;
+		geno_one<KMAX, true>(p, base, init, tape, i, j, qf);
 	}
 }
 
@@ -437,6 +466,73 @@ __global__ void __launch_bounds__(256) k4_sweep_counts(PolyDev p, int chunk, int
 			const unsigned g0 = g & 0xff, g1 = (g >> 8) & 0xff, g2 = (g >> 16) & 0xff, g3 = g >> 24;
 			if (same) {
 				atomicAdd(&p.ccnt[((size_t)(z & 0xff) * p.L + j) * p.GS + poly_gid(p, j, g0, g1, g2, g3)], 1);
+			} else if (ALLO) { /* get_cat_allo (poly_geno.c:1341-1372) */
+				ncat[(g0 != g1 ? 2 : 0) + (g2 != g3 ? 1 : 0)]++;
+			} else {
+				/* get_cat_auto (poly_geno.c:1313-1339): distinct alleles; two of them: 2+2 or 3+1 */
+				const int nd = 1 + (g1 != g0) + (g2 != g0 && g2 != g1) + (g3 != g0 && g3 != g1 && g3 != g2);
+				const int m0 = 1 + (g1 == g0) + (g2 == g0) + (g3 == g0);
+				ncat[nd == 1 ? 0 : nd == 2 ? (m0 == 2 ? 2 : 1) : nd]++;
+			}
+		}
+	}
+	if (TILE) {
+		__syncthreads();
+		for (int e = threadIdx.x; e < 2 * AK * 64; e += 256) {
+			const int v = tile[e];
+			const int l = e & 63, r = e >> 6, jj = blockIdx.x * 64 + l;
+			if (v && jj < p.L) {
+				if (r < AK) atomicAdd(&p.cnt[(size_t)jj * AK + r], v);
+				else atomicAdd(&cntmix[(size_t)jj * AK + (r - AK)], v);
+			}
+		}
+	}
+#pragma unroll
+	for (int q = 1; q < 5; q++) {
+		unsigned v = ncat[q];
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+		if (lane == 0 && v) atomicAdd(&catcnt[q], (unsigned long long)v);
+	}
+}
+
+/* the same sweep in a wide-allele context: same-cluster loci find their row in closed form.  (A copy rather than a shared body: with the
+ * body in a function the existing kernel compiled to one more SGPR.) */
+template <bool TILE, bool ALLO>
+__global__ void __launch_bounds__(256) k4_sweep_counts_w(PolyDev p, int chunk, int *cntmix, unsigned long long *catcnt)
+{
+	extern __shared__ int tile[]; /* [2][Amax * K][64] */
+	const int AK = p.Amax * p.K, lane = (int)lane_id(), wave = threadIdx.x >> 6;
+	const int j = blockIdx.x * 64 + lane, i0 = blockIdx.y * chunk, i1 = min(p.N, i0 + chunk);
+	if (TILE) {
+		for (int e = threadIdx.x; e < 2 * AK * 64; e += 256) tile[e] = 0;
+		__syncthreads();
+	}
+	unsigned ncat[5] = {0, 0, 0, 0, 0};
+	if (j < p.L) {
+		for (int i = i0 + wave; i < i1; i += 4) {
+			const size_t id = (size_t)i * p.Lp + j;
+			const unsigned g = *(const unsigned *)(p.geno + id * 4);
+			if ((g & 0xff) == 0xff) continue;
+			const unsigned z = *(const unsigned *)(p.z + id * 4);
+			const bool same = (z == (z & 0xff) * 0x01010101u);
+#pragma unroll
+			for (int c = 0; c < 4; c++) {
+				const int a = (g >> (8 * c)) & 0xff, k = (z >> (8 * c)) & 0xff;
+				if (TILE) {
+					atomicAdd(&tile[(a * p.K + k) * 64 + lane], 1);
+					if (!same) atomicAdd(&tile[(AK + a * p.K + k) * 64 + lane], 1);
+				} else if (ALLO && c >= 2) { /* the second subgenome's copies (seqpop2, poly_geno.c:481-492) */
+					atomicAdd(&p.cnt2[((size_t)j * p.Amax + a) * p.K + k], 1);
+					if (!same) atomicAdd(&p.cntmix2[((size_t)j * p.Amax + a) * p.K + k], 1);
+				} else {
+					atomicAdd(&p.cnt[((size_t)j * p.Amax + a) * p.K + k], 1);
+					if (!same) atomicAdd(&cntmix[((size_t)j * p.Amax + a) * p.K + k], 1);
+				}
+			}
+			const unsigned g0 = g & 0xff, g1 = (g >> 8) & 0xff, g2 = (g >> 16) & 0xff, g3 = g >> 24;
+			if (same) {
+				atomicAdd(&p.ccnt[((size_t)(z & 0xff) * p.L + j) * p.GS + poly_row_w<ALLO>(p, j, g0, g1, g2, g3)], 1);
 			} else if (ALLO) { /* get_cat_allo (poly_geno.c:1341-1372) */
 				ncat[(g0 != g1 ? 2 : 0) + (g2 != g3 ? 1 : 0)]++;
 			} else {
@@ -519,6 +615,208 @@ __global__ void k4_genfreq(PolyDev p, const float *self, int own)
 	if (e) atomicOr(p.err, 4u); /* the reference stops on it for current and proposed rates alike (poly_geno.c:2021-2025) */
 }
 
+/*
+ * Wide-allele contexts (more than 16 alleles at some locus, up to 32): the table kernels above run ONE lane per (cluster, locus) and find every
+ * row by linear search (isg_poly_find, O(G) per term), which no longer scales.  Here a workgroup takes one (cluster, locus) table.
+ *   k4_exfreq_w   lanes over the genotypes, the table's allele frequencies staged in LDS; each entry is exfreq_row's / exfreq_row_allo's
+ *                 expression for that row (same float / double pattern, same bits)
+ *   k4_genfreq_w  the classes in dependency order with a workgroup barrier between them -- autotetraploid: quadri -> tri triples (3x3 solve
+ *                 per triple) -> duplex -> simplex -> mono; allotetraploid: ijkl -> ijkk and iikl -> iikk.  Within a class every row depends
+ *                 only on rows of earlier classes, so a lane forms its row's sum term by term in genfreq_row's order (the `sic` reuse and the
+ *                 n >= 3 / n >= 4 branches included) and the row comes out as genfreq_row computes it; rows are found in closed form
+ *                 (isg_poly_rank, isg_allo_row_any).
+ */
+__device__ __forceinline__ float exfreq_auto_at(const isg_polyclass &pc, const double *f, int r)
+{
+	const int n = pc.n, P = 4;
+	int tmp = pc.list[r], digit[4];
+	int b = pc.g[1];
+	if (r < b) return (float)isg_log(f[tmp % n]) * (float)P;
+	if (r < (b += pc.g[2])) {
+		digit[0] = tmp % n;
+		tmp /= n;
+		digit[1] = tmp % n;
+		return (float)(isg_log(4.0) + isg_log(f[digit[1]]) * (float)(P - 1) + isg_log(f[digit[0]]));
+	}
+	if (r < (b += pc.g[3])) {
+		digit[0] = tmp % n;
+		tmp /= (n * n);
+		digit[1] = tmp % n;
+		return (float)(isg_log(6.0) + (isg_log(f[digit[1]]) + isg_log(f[digit[0]])) * (P / 2));
+	}
+	if (r < (b += pc.g[4])) {
+		for (int m = 0; m < P - 1; m++) { digit[m] = tmp % n; tmp /= n; }
+		return (float)(isg_log(12.0) + isg_log(f[digit[2]]) * (P / 2) + isg_log(f[digit[0]]) + isg_log(f[digit[1]]));
+	}
+	for (int m = 0; m < P; m++) { digit[m] = tmp % n; tmp /= n; }
+	float ex = (float)isg_log(24.0);
+	for (int m = 0; m < P; m++) ex += (float)isg_log(f[digit[m]]);
+	return ex;
+}
+__device__ __forceinline__ float exfreq_allo_at(const isg_polyclass &pc, const double *f, const double *f2, int r)
+{
+	const int n = pc.n, code = pc.list[r], d0 = code % n, d1 = (code / n) % n, d2 = (code / n / n) % n, d3 = code / n / n / n;
+	if (r < pc.g[1]) return (float)((isg_log(f[d2]) + isg_log(f2[d0])) * 2);
+	if (r < pc.g[1] + pc.g[2]) return (float)(isg_log(2.0) + isg_log(f[d2]) * 2 + isg_log(f2[d0]) + isg_log(f2[d1]));
+	if (r < pc.g[1] + pc.g[2] + pc.g[3]) return (float)(isg_log(2.0) + isg_log(f2[d1]) * 2 + isg_log(f[d3]) + isg_log(f[d2]));
+	float ex = (float)isg_log(4.0);
+	ex += (float)isg_log(f2[d0]);
+	ex += (float)isg_log(f2[d1]);
+	ex += (float)isg_log(f[d2]);
+	ex += (float)isg_log(f[d3]);
+	return ex;
+}
+
+/* calc_exfreq_auto / calc_exfreq_allo: one workgroup per (cluster, locus) table, blockIdx.x = k L + j */
+template <bool ALLO>
+__global__ void __launch_bounds__(256) k4_exfreq_w(PolyDev p)
+{
+	__shared__ double fs[2][ISG_POLY_ACAP_W];
+	const int id = (int)blockIdx.x, k = id / p.L, j = id - k * p.L, t = (int)threadIdx.x;
+	const isg_polyclass pc = p.pc[p.lclass[j]];
+	if (t < pc.n) {
+		fs[0][t] = p.freq[((size_t)j * p.Amax + t) * p.KP + k];
+		if (ALLO) fs[1][t] = p.freq2[((size_t)j * p.Amax + t) * p.KP + k];
+	}
+	__syncthreads();
+	float *ex = p.exfreq + (size_t)id * p.GS;
+	for (int r = t; r < pc.G; r += 256) ex[r] = ALLO ? exfreq_allo_at(pc, fs[0], fs[1], r) : exfreq_auto_at(pc, fs[0], r);
+}
+
+/* auto_genfreq / allo_genfreq at the selfing rates self[k] into genofreq (own) or tabtmp: one workgroup per table, blockIdx.x = k L + j */
+template <bool ALLO>
+__global__ void __launch_bounds__(256) k4_genfreq_w(PolyDev p, const float *self, int own)
+{
+	const int id = (int)blockIdx.x, k = id / p.L, j = id - k * p.L, t = (int)threadIdx.x;
+	const isg_polyclass pc = p.pc[p.lclass[j]];
+	const int n = pc.n, G = pc.G, b1 = pc.g[1], b2 = b1 + pc.g[2], b3 = b2 + pc.g[3], b4 = b3 + pc.g[4];
+	const float s = self[k];
+	const float *ex = p.exfreq + (size_t)id * p.GS;
+	float *fr = (own ? p.genofreq : p.tabtmp) + (size_t)id * p.GS;
+	int e = 0;
+	if (ALLO) {
+		for (int r = b3 + t; r < G; r += 256) { /* ijkl */
+			fr[r] = (float)(isg_log((double)(1 - s)) + ex[r] - isg_log((double)(1 - s / 4)));
+			if (fr[r] > 0) e |= 4;
+		}
+		__syncthreads();
+		for (int r = b1 + t; r < b3; r += 256) { /* iikl and ijkk: both from ijkl rows only */
+			const int code = pc.list[r];
+			float temp = 0;
+			if (r >= b2) { /* ijkk */
+				const int kk = code % n, b = (code / n / n) % n, a = code / n / n / n;
+				for (int v = 0; v < n; v++)
+					if (v != kk) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, b, kk, v)]) * s / 8.0);
+			} else { /* iikl */
+				const int d = code % n, c = (code / n) % n, a = (code / n / n) % n;
+				for (int v = 0; v < n; v++)
+					if (v != a) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, v, c, d)]) * s / 8.0);
+			}
+			fr[r] = (float)(isg_log((1 - s) * isg_exp((double)ex[r]) + temp) - isg_log(1 - s / 2.0));
+			if (fr[r] > 0) e |= 4;
+		}
+		__syncthreads();
+		for (int r = t; r < b1; r += 256) { /* iikk */
+			const int code = pc.list[r], kk = code % n, a = (code / n / n) % n;
+			float temp = 0;
+			for (int v = 0; v < n; v++)
+				if (v != kk) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, a, kk, v)]) * s / 4.0);
+			for (int v = 0; v < n; v++)
+				if (v != a) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, v, kk, kk)]) * s / 4.0);
+			for (int v = 0; v < n; v++)
+				for (int w = 0; w < n; w++)
+					if (v != a && w != kk) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, v, kk, w)]) * s / 16.0);
+			fr[r] = (float)(isg_log((1 - s) * isg_exp((double)ex[r]) + temp) - isg_log((double)(1 - s)));
+			if (fr[r] > 0) e |= 4;
+		}
+	} else {
+		if (n >= 4)
+			for (int i = b4 + t; i < G; i += 256) { /* quadri ijkl */
+				fr[i] = (float)(isg_log((double)(1 - s)) + ex[i] - isg_log((double)(1 - s / 6)));
+				if (fr[i] > 0) e |= 4;
+			}
+		__syncthreads();
+		if (n >= 3)
+			for (int q = t; q < pc.g[4] / 3; q += 256) { /* tri iijk: one lane per triple */
+				const int r0 = b3 + 3 * q;
+				int num = pc.list[r0], digit[3];
+				for (int m = 2; m >= 0; m--) { digit[m] = num % n; num /= n; }
+				float temp = 0, matr[4][4], vec[4];
+				if (n >= 4) {
+					for (int l = 0; l < n; l++)
+						if (l != digit[0] && l != digit[1] && l != digit[2]) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, digit[0], digit[1], digit[2], l)]));
+					if (temp > 1) e |= 4;
+				}
+				for (int a = 1; a <= 3; a++) {
+					for (int b = 1; b <= 3; b++) {
+						if (a == b) matr[a][b] = (float)(1 - s * 10.0 / 36.0);
+						else matr[a][b] = (float)(-s / 9.0);
+					}
+					vec[a] = (float)(s / 18.0 * temp + (1.0 - s) * isg_exp((double)ex[r0 + a - 1]));
+				}
+				temp = vec[1];
+				for (int a = 1; a <= 3; a++) vec[a] /= temp;
+				isg_poly_gaussj3(matr, vec, &e);
+				for (int a = 0; a < 3; a++) {
+					fr[r0 + a] = (float)(isg_log((double)vec[a + 1]) + isg_log((double)temp));
+					if (fr[r0 + a] > 0) e |= 4;
+				}
+			}
+		__syncthreads();
+		for (int i = b2 + t; i < b3; i += 256) { /* duplex iijj */
+			int num = pc.list[i];
+			const int d0 = num % n;
+			num /= (n * n);
+			const int d1 = num % n;
+			float temp = 0;
+			if (n >= 3)
+				for (int x = 0; x < n; x++)
+					if (x != d0 && x != d1) {
+						temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d1, d1, d0, x)]) / 9.0 * s);
+						temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d0, d0, d1, x)]) / 9.0 * s);
+						temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, x, x, d1, d0)]) / 36.0 * s);
+						if (n >= 4)
+							for (int y = x + 1; y < n; y++)
+								if (y != d0 && y != d1) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d0, d1, x, y)]) / 36.0 * s);
+					}
+			fr[i] = (float)(isg_log((1 - s) * isg_exp((double)ex[i]) + temp) - isg_log(1 - s / 2.0));
+			if (fr[i] > 0) e |= 4;
+		}
+		__syncthreads();
+		for (int i = b1 + t; i < b2; i += 256) { /* simplex iiij */
+			int num = pc.list[i];
+			const int d0 = num % n;
+			num /= n;
+			const int d1 = num % n;
+			float temp = (float)(8.0 / 36.0 * isg_exp((double)fr[isg_poly_rank(n, d0, d0, d1, d1)]) * s);
+			if (n >= 3)
+				for (int x = 0; x < n; x++)
+					if (x != d0 && x != d1) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d1, d1, d0, x)]) / 9.0 * s);
+			fr[i] = (float)(isg_log((1 - s) * isg_exp((double)ex[i]) + temp) - isg_log(1 - s / 2.0));
+			if (fr[i] > 0) e |= 4;
+		}
+		__syncthreads();
+		for (int i = t; i < b1; i += 256) { /* mono iiii */
+			const int a = pc.list[i] % n;
+			float temp = 0;
+			for (int x = 0; x < n; x++)
+				if (x != a) {
+					int row = isg_poly_rank(n, a, a, a, x);
+					temp = (float)(temp + isg_exp((double)fr[row]) / 4.0 * s);
+					/* sic (as genfreq_row): for a > x the duplex term reuses the simplex row */
+					if (a < x) row = isg_poly_rank(n, a, a, x, x);
+					temp = (float)(temp + isg_exp((double)fr[row]) / 36.0 * s);
+					if (n >= 3)
+						for (int y = x + 1; y < n; y++)
+							if (y != a) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, a, a, x, y)]) / 36.0 * s);
+				}
+			fr[i] = (float)(isg_log((1 - s) * isg_exp((double)ex[i]) + temp) - isg_log((double)(1 - s)));
+			if (fr[i] > 0) e |= 4;
+		}
+	}
+	if (e) atomicOr(p.err, 4u);
+}
+
 /* D = sum over (locus, genotype) of count * table value: blockIdx.y = k for the current tables (slot 1 + k),
  * K + k for the proposal tables (slot 1 + K + k) */
 __global__ void __launch_bounds__(256) k4_dsum(PolyDev p)
@@ -535,6 +833,25 @@ __global__ void __launch_bounds__(256) k4_dsum(PolyDev p)
 			const unsigned c = (unsigned)p.ccnt[e];
 			if (c) acc_add_times(&a, (double)(use_tmp ? p.tabtmp[e] : p.genofreq[e]), c);
 		}
+	}
+	const isg_acc r = block_reduce_acc<256>(a, sm);
+	if (threadIdx.x == 0) acc_global_add(p.accbuf + 5 * (1 + (int)blockIdx.y), r);
+}
+/* the same sums in a wide-allele context (up to 278 784 genotypes per locus: one lane per entry made the block reductions and their atomics
+ * the cost): a workgroup per (locus, blockIdx.y), its lanes striding over the locus' own genotypes.  The accumulators are exact integers,
+ * so the grouping does not change the sums. */
+__global__ void __launch_bounds__(256) k4_dsum_w(PolyDev p)
+{
+	__shared__ unsigned long long sm[4 * 5];
+	const int use_tmp = (int)blockIdx.y >= p.K, k = (int)blockIdx.y - (use_tmp ? p.K : 0), j = (int)blockIdx.x;
+	const int G = p.pc[p.lclass[j]].G;
+	const size_t row = ((size_t)k * p.L + j) * p.GS;
+	const float *tab = use_tmp ? p.tabtmp : p.genofreq;
+	isg_acc a;
+	isg_acc_zero(&a);
+	for (int g = (int)threadIdx.x; g < G; g += 256) {
+		const unsigned c = (unsigned)p.ccnt[row + g];
+		if (c) acc_add_times(&a, (double)tab[row + g], c);
 	}
 	const isg_acc r = block_reduce_acc<256>(a, sm);
 	if (threadIdx.x == 0) acc_global_add(p.accbuf + 5 * (1 + (int)blockIdx.y), r);
@@ -562,8 +879,8 @@ __global__ void k4_logfreq(PolyDev p)
 /* Four loci per lane and pass, every stage of the lookup chain (observation / genotype / assignment -> locus class -> class size and map offset ->
  * table row -> term) issued for all four before the next stage needs it: the chain is five dependent memory round trips, and one locus at a time the
  * waves waited for them 80 % of their cycles (SQ counters: 10 us per pass). */
-template <bool ALLO>
-__global__ void __launch_bounds__(256) k4_lkd(PolyDev p)
+template <bool ALLO, bool WIDE>
+__device__ __forceinline__ void lkd_body(const PolyDev &p)
 {
 	__shared__ unsigned long long sm[4 * 5];
 	const int i = blockIdx.x;
@@ -587,7 +904,7 @@ __global__ void __launch_bounds__(256) k4_lkd(PolyDev p)
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
 			n[u] = p.pc[cl[u]].n;
-			off[u] = p.gidoff[cl[u]];
+			off[u] = WIDE ? 0 : p.gidoff[cl[u]];
 		}
 		int gid[4];
 		bool same[4];
@@ -595,7 +912,8 @@ __global__ void __launch_bounds__(256) k4_lkd(PolyDev p)
 		for (int u = 0; u < 4; u++) {
 			const unsigned g0 = g[u] & 0xff, g1 = (g[u] >> 8) & 0xff, g2 = (g[u] >> 16) & 0xff, g3 = g[u] >> 24;
 			const unsigned code = ok[u] ? ((g0 * n[u] + g1) * n[u] + g2) * n[u] + g3 : 0u; /* (poly_gid) */
-			gid[u] = p.gidmap[off[u] + (int)code];
+			if (WIDE) gid[u] = !ok[u] ? 0 : ALLO ? isg_allo_row(n[u], (int)g0, (int)g1, (int)g2, (int)g3) : isg_poly_rank(n[u], (int)g0, (int)g1, (int)g2, (int)g3);
+			else gid[u] = p.gidmap[off[u] + (int)code];
 			same[u] = (z[u] == (z[u] & 0xff) * 0x01010101u);
 		}
 		float gf[4];
@@ -625,6 +943,16 @@ __global__ void __launch_bounds__(256) k4_lkd(PolyDev p)
 	}
 	const isg_acc r = block_reduce_acc<256>(a, sm);
 	if (threadIdx.x == 0) p.indvlkh[i] = isg_acc_value(&r);
+}
+template <bool ALLO>
+__global__ void __launch_bounds__(256) k4_lkd(PolyDev p)
+{
+	lkd_body<ALLO, false>(p);
+}
+template <bool ALLO>
+__global__ void __launch_bounds__(256) k4_lkd_w(PolyDev p) /* wide-allele contexts: closed-form rows */
+{
+	lkd_body<ALLO, true>(p);
 }
 
 /* update_ZQ (poly_geno.c:750-836): one workgroup walks the individuals in stream order */
@@ -1213,14 +1541,27 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 	const int N = cfg->N, L = cfg->L, K = cfg->K;
 	int Amax = 1;
 	for (int j = 0; j < L; j++) Amax = allelenum[j] > Amax ? allelenum[j] : Amax;
-	if (Amax > ISG_POLY_ACAP) return fail("isg_ctx_create: ploidy 4 supports up to 16 alleles per locus in this build");
+	if (Amax > ISG_POLY_ACAP_W) return fail("isg_ctx_create: ploidy 4 supports up to 32 alleles per locus in this build");
+	const bool wide = Amax > ISG_POLY_ACAP;
 	const int allo = cfg->reserved[0] ? 1 : 0; /* isg_config.allo: allotetraploid, -ap 0 */
 	for (int j = 0; j < L; j++) /* 0 = nobody typed at this locus: kept, never used (transform_data2 does not drop loci) */
 		if (allelenum[j] < 0) return fail("isg_ctx_create: negative allele count");
+	{ /* the five tables padded to GS = G(Amax) rows (exfreq, genofreq, genofreqT, tabtmp, ccnt): at most half of what the device has free */
+		const int GS = allo ? isg_allo_G(Amax) : isg_poly_G(Amax);
+		const size_t tb = sizeof(float) * (size_t)K * (size_t)GS * (4 * (size_t)L + (size_t)((L + 3) & ~3));
+		size_t fr = 0, tot = 0;
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = (size_t)1 << 31;
+		if (tb > fr / 2) {
+			char msg[256];
+			snprintf(msg, sizeof msg, "isg_ctx_create_poly: the genotype tables need %zu bytes (%d genotypes per locus, K %d, L %d): more than half of the free device memory", tb, GS, K, L);
+			return fail(msg);
+		}
+	}
 	isg_ctx *c = new isg_ctx();
 	PolyCtx *pc = new PolyCtx();
 	memset(&pc->p, 0, sizeof(pc->p));
 	c->poly = pc;
+	pc->wide = wide;
 	c->cfg = *cfg;
 	ctx_count(c, +1);
 	CtxGuard guard(c); /* any early return below releases what has been allocated so far */
@@ -1248,10 +1589,12 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 		cls[q].n = n;
 		cls[q].G = cls[q].g[0];
 		GS = cls[q].G > GS ? cls[q].G : GS;
+		if (wide) continue; /* rows in closed form (isg_poly_rank, isg_allo_row): no map */
 		gidoff[q] = (int)gidmap.size();
 		gidmap.resize(gidmap.size() + (size_t)n * n * n * n, (short)-1);
 		for (int g = 0; g < cls[q].G; g++) gidmap[gidoff[q] + pc->lists[q][g]] = (short)g;
 	}
+	if (wide) gidmap.assign(1, (short)-1);
 	pc->lclass_h.resize(L);
 	for (int j = 0; j < L; j++)
 		for (int q = 0; q < ncls; q++)
@@ -1405,7 +1748,7 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 	c->cnt_h.assign((size_t)L * Amax * K, 0);
 	pin_host(c, c->cnt_h.data(), sizeof(int) * c->cnt_h.size());
 	pin_host(c, c->freq_stage.data(), sizeof(double) * c->freq_stage.size());
-	pc->tab_h.assign((size_t)K * L * GS, 0.f);
+	if (!wide) pc->tab_h.assign((size_t)K * L * GS, 0.f);
 	c->alpha = 0;
 	c->totallkh = 0;
 	c->iter = 0;
@@ -1473,7 +1816,15 @@ static int poly_geno_sweep(isg_ctx *c, int init)
 	const dim3 ggrid((unsigned)(((ntile + 7) / 8) * 8 * nchunk));
 #define GENO_LAUNCH(KM) do { if (p.allo) hipLaunchKernelGGL((k4_geno<KM, true>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk); \
 	else hipLaunchKernelGGL((k4_geno<KM, false>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk); } while (0)
-	if (p.K <= 4) GENO_LAUNCH(4);
+	if (c->poly->wide && !p.allo) {
+#define GENO_W(KM) hipLaunchKernelGGL((k4_geno_w<KM>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk)
+		if (p.K <= 4) GENO_W(4);
+		else if (p.K <= 8) GENO_W(8);
+		else if (p.K <= 12) GENO_W(12);
+		else if (p.K <= 16) GENO_W(16);
+		else GENO_W(32);
+#undef GENO_W
+	} else if (p.K <= 4) GENO_LAUNCH(4);
 	else if (p.K <= 8) GENO_LAUNCH(8);
 	else if (p.K <= 12) GENO_LAUNCH(12);
 	else if (p.K <= 16) GENO_LAUNCH(16);
@@ -1505,13 +1856,42 @@ static int poly_sweep_counts(isg_ctx *c)
 	const int chunk = p.N > 4096 ? 1024 : (p.N + 3) / 4;
 	const dim3 grid((L + 63) / 64, (p.N + chunk - 1) / chunk);
 	prof_begin(c);
-	if (p.allo) hipLaunchKernelGGL((k4_sweep_counts<false, true>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+	if (pc->wide) {
+		if (p.allo) hipLaunchKernelGGL((k4_sweep_counts_w<false, true>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+		else if (lds <= 60000) hipLaunchKernelGGL((k4_sweep_counts_w<true, false>), grid, dim3(256), lds, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+		else hipLaunchKernelGGL((k4_sweep_counts_w<false, false>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+	} else if (p.allo) hipLaunchKernelGGL((k4_sweep_counts<false, true>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
 	else if (lds <= 60000) hipLaunchKernelGGL((k4_sweep_counts<true, false>), grid, dim3(256), lds, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
 	else hipLaunchKernelGGL((k4_sweep_counts<false, false>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
 	prof_end(c, "k4_sweep_counts");
 	HIPCHK(hipGetLastError());
 	pc->counts_valid = true;
 	return 0;
+}
+
+/* calc_exfreq_auto / _allo for every (cluster, locus) table */
+static void poly_launch_exfreq(isg_ctx *c)
+{
+	const PolyDev &p = c->poly->p;
+	const int K = p.K, L = p.L;
+	if (c->poly->wide) {
+		if (p.allo) hipLaunchKernelGGL(k4_exfreq_w<true>, dim3((unsigned)(K * L)), dim3(256), 0, c->stream, p);
+		else hipLaunchKernelGGL(k4_exfreq_w<false>, dim3((unsigned)(K * L)), dim3(256), 0, c->stream, p);
+		return;
+	}
+	do { if (p.allo) hipLaunchKernelGGL(k4_exfreq<true>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); else hipLaunchKernelGGL(k4_exfreq<false>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); } while (0);
+}
+/* auto_genfreq / allo_genfreq for every table at the rates self[k]: into genofreq (own) or tabtmp */
+static void poly_launch_genfreq(isg_ctx *c, const float *self, int own)
+{
+	const PolyDev &p = c->poly->p;
+	const int K = p.K, L = p.L;
+	if (c->poly->wide) {
+		if (p.allo) hipLaunchKernelGGL(k4_genfreq_w<true>, dim3((unsigned)(K * L)), dim3(256), 0, c->stream, p, self, own);
+		else hipLaunchKernelGGL(k4_genfreq_w<false>, dim3((unsigned)(K * L)), dim3(256), 0, c->stream, p, self, own);
+		return;
+	}
+	do { if (p.allo) hipLaunchKernelGGL(k4_genfreq<true>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own); else hipLaunchKernelGGL(k4_genfreq<false>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own); } while (0);
 }
 
 static int poly_update_P(isg_ctx *c) /* update_P_auto */
@@ -1526,8 +1906,8 @@ static int poly_update_P(isg_ctx *c) /* update_P_auto */
 		HIPCHK(hipGetLastError());
 		if (refresh_freqf(c)) return 1;
 		prof_begin(c);
-		do { if (p.allo) hipLaunchKernelGGL(k4_exfreq<true>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); else hipLaunchKernelGGL(k4_exfreq<false>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); } while (0);
-		prof_end(c, "k4_exfreq");
+		poly_launch_exfreq(c);
+		prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
 		HIPCHK(hipGetLastError());
 		c->poly->freq_host = false;
 		return 0;
@@ -1538,8 +1918,8 @@ static int poly_update_P(isg_ctx *c) /* update_P_auto */
 		if (done) {
 			if (refresh_freqf(c)) return 1;
 			prof_begin(c);
-			do { if (p.allo) hipLaunchKernelGGL(k4_exfreq<true>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); else hipLaunchKernelGGL(k4_exfreq<false>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); } while (0);
-			prof_end(c, "k4_exfreq");
+			poly_launch_exfreq(c);
+			prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
 			HIPCHK(hipGetLastError());
 			c->poly->freq_host = false;
 			return 0;
@@ -1601,8 +1981,8 @@ static int poly_update_P(isg_ctx *c) /* update_P_auto */
 	if (refresh_freqf(c)) return 1; /* single precision rows for the Z pre-filter */
 	/* calc_exfreq_auto follows update_P_auto in the chain loop (poly_geno.c:102-103) */
 	prof_begin(c);
-	do { if (p.allo) hipLaunchKernelGGL(k4_exfreq<true>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); else hipLaunchKernelGGL(k4_exfreq<false>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); } while (0);
-	prof_end(c, "k4_exfreq");
+	poly_launch_exfreq(c);
+	prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -1670,11 +2050,11 @@ static int poly_update_S_POP(isg_ctx *c) /* poly_geno.c:584-643 */
 	HIPCHK(hipMemcpyAsync(c->poly->d_self, selfs, sizeof(selfs), hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemsetAsync(p.accbuf, 0, sizeof(unsigned long long) * 5 * (2 * ISG_KCAP + 2), c->stream));
 	prof_begin(c);
-	do { if (p.allo) hipLaunchKernelGGL(k4_genfreq<true>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, (const float *)c->poly->d_self, 1); else hipLaunchKernelGGL(k4_genfreq<false>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, (const float *)c->poly->d_self, 1); } while (0);
-	prof_end(c, "k4_genfreq");
+	poly_launch_genfreq(c, (const float *)c->poly->d_self, 1);
+	prof_end(c, c->poly->wide ? "k4_genfreq_w" : "k4_genfreq");
 	prof_begin(c);
-	do { if (p.allo) hipLaunchKernelGGL(k4_genfreq<true>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, (const float *)(c->poly->d_self + ISG_KCAP), 0); else hipLaunchKernelGGL(k4_genfreq<false>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, (const float *)(c->poly->d_self + ISG_KCAP), 0); } while (0);
-	prof_end(c, "k4_genfreq");
+	poly_launch_genfreq(c, (const float *)(c->poly->d_self + ISG_KCAP), 0);
+	prof_end(c, c->poly->wide ? "k4_genfreq_w" : "k4_genfreq");
 	{ /* the terms that no selfing rate touches (slot 0), from the counts of the iteration's sweep */
 		const size_t ne = (size_t)L * p.Amax * K;
 		prof_begin(c);
@@ -1683,7 +2063,8 @@ static int poly_update_S_POP(isg_ctx *c) /* poly_geno.c:584-643 */
 		prof_end(c, "k4_mixsum");
 	}
 	prof_begin(c);
-	hipLaunchKernelGGL(k4_dsum, dim3((unsigned)((nt + 255) / 256), 2 * K), dim3(256), 0, c->stream, p);
+	if (c->poly->wide) hipLaunchKernelGGL(k4_dsum_w, dim3((unsigned)L, 2 * K), dim3(256), 0, c->stream, p);
+	else hipLaunchKernelGGL(k4_dsum, dim3((unsigned)((nt + 255) / 256), 2 * K), dim3(256), 0, c->stream, p);
 	prof_end(c, "k4_dsum");
 	HIPCHK(hipGetLastError());
 	unsigned long long catcnt[8];
@@ -1867,7 +2248,10 @@ static int poly_cal_lkh(isg_ctx *c)
 	hipLaunchKernelGGL(k4_logfreq, dim3((unsigned)(((size_t)p.L * p.Amax * p.KP + (size_t)p.K * p.GS * p.L + 255) / 256)), dim3(256), 0, c->stream, p);
 	prof_end(c, "k4_logfreq");
 	prof_begin(c);
-	if (p.allo) hipLaunchKernelGGL(k4_lkd<true>, dim3(p.N), dim3(256), 0, c->stream, p);
+	if (c->poly->wide) {
+		if (p.allo) hipLaunchKernelGGL(k4_lkd_w<true>, dim3(p.N), dim3(256), 0, c->stream, p);
+		else hipLaunchKernelGGL(k4_lkd_w<false>, dim3(p.N), dim3(256), 0, c->stream, p);
+	} else if (p.allo) hipLaunchKernelGGL(k4_lkd<true>, dim3(p.N), dim3(256), 0, c->stream, p);
 	else hipLaunchKernelGGL(k4_lkd<false>, dim3(p.N), dim3(256), 0, c->stream, p);
 	prof_end(c, "k4_lkd");
 	prof_begin(c);

@@ -71,6 +71,40 @@ static inline void isg_poly_build(int i, int g[6], int *list)
 				for (n = m + 1; n < i; n++) list[tmp + cnt++] = j * i * i * i + k * i * i + i * m + n;
 }
 
+/*
+ * Closed-form row of an autotetraploid genotype in isg_poly_build's order, from the multiset of its four allele codes (any order,
+ * each < n).  With C(m, r) the binomial and rank_r(c_0 < .. < c_{r-1}) = C(n, r) - 1 - sum_i C(n - 1 - c_i, r - i) the rank of a
+ * combination in lexicographic order:
+ *   iiii  a | iiij  g1 + 2 rank_2(min, max) + (triple allele is the larger) | iijj  g1 + g2 + rank_2 | iijk  g1 + g2 + g3 + 3 rank_3(i, j, k)
+ *   + (position of the doubled allele among the three) | ijkl  g1 + g2 + g3 + g4 + rank_4.  The wide-allele kernels use it instead of a
+ * code -> row map (n^4 entries, rows beyond a short above 16 alleles).
+ */
+ISG_HD int isg_poly_binom(int m, int r)
+{
+	return r == 1 ? m : r == 2 ? m * (m - 1) / 2 : r == 3 ? m * (m - 1) * (m - 2) / 6 : m * (m - 1) * (m - 2) * (m - 3) / 24;
+}
+ISG_HD int isg_poly_rank(int n, int a, int b, int c, int d)
+{
+	int t;
+#define ISG_CSWAP(x, y) if (x > y) { t = x; x = y; y = t; }
+	ISG_CSWAP(a, b) ISG_CSWAP(c, d) ISG_CSWAP(a, c) ISG_CSWAP(b, d) ISG_CSWAP(b, c) /* a <= b <= c <= d */
+#undef ISG_CSWAP
+	const int g2 = n * (n - 1), g3 = g2 / 2, g4 = n * (n - 1) * (n - 2) / 2, C2 = g3, C3 = g4 / 3;
+	if (a == d) return a;
+	if (a == c || b == d) { /* simplex: the triple allele is a (a a a d) or d (a d d d) */
+		const int r2 = C2 - 1 - isg_poly_binom(n - 1 - a, 2) - isg_poly_binom(n - 1 - d, 1);
+		return n + 2 * r2 + (a == c ? 0 : 1);
+	}
+	if (a == b && c == d) return n + g2 + C2 - 1 - isg_poly_binom(n - 1 - a, 2) - isg_poly_binom(n - 1 - c, 1);
+	if (a == b || b == c || c == d) { /* tri: the three distinct alleles x < y < z, the doubled one at position q */
+		const int x = a, y = (a == b) ? c : b, z = d, q = (a == b) ? 0 : (b == c) ? 1 : 2;
+		const int r3 = C3 - 1 - isg_poly_binom(n - 1 - x, 3) - isg_poly_binom(n - 1 - y, 2) - isg_poly_binom(n - 1 - z, 1);
+		return n + g2 + g3 + 3 * r3 + q;
+	}
+	return n + g2 + g3 + g4 + isg_poly_binom(n, 4) - 1 - isg_poly_binom(n - 1 - a, 4) - isg_poly_binom(n - 1 - b, 3) - isg_poly_binom(n - 1 - c, 2) -
+	       isg_poly_binom(n - 1 - d, 1);
+}
+
 ISG_HD int isg_poly_exists(int value, const int *vec, int leng) /* data_interface.c:865-877 */
 {
 	int i, flag = 0;
