@@ -27,6 +27,8 @@
  * Compile with -ffp-contract=off: isg_math.h relies on plain IEEE operations.
  */
 #include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,6 +45,7 @@
 #include "isg_math.h"
 #include "isg_wh.h"
 #include "isg_sampler.h"
+#include "isg_kdispatch.h"
 
 #define ISG_KCAP 32  /* K of the register-resident kernel instances, and of ploidy 4 */
 #define ISG_KWIDE 64 /* diploid K above ISG_KCAP: the K-generic wide kernels (DESIGN.md §4 "K up to 64") */
@@ -54,6 +57,11 @@ static int fail(const std::string &m)
 	g_err = m;
 	return 1;
 }
+/* Environment switches, from getenv's answer e.  A flag leaves its default only for the opposite value: 0 turns a
+ * default-on switch off, 1 turns a default-off switch on.  A number outside [lo, hi] is ignored: the default. */
+static bool env_flag(const char *e, bool def) { return e ? (def ? atoi(e) != 0 : atoi(e) == 1) : def; }
+static long env_int(const char *e, long def, long lo = LONG_MIN, long hi = LONG_MAX) { return (e && atol(e) >= lo && atol(e) <= hi) ? atol(e) : def; }
+static double env_double(const char *e, double def, double lo, double hi = HUGE_VAL) { return (e && atof(e) >= lo && atof(e) <= hi) ? atof(e) : def; }
 #define HIPCHK(x)                                                                                     \
 	do {                                                                                          \
 		hipError_t e_ = (x);                                                                  \
@@ -391,11 +399,11 @@ __global__ void k_count_atomic(DevView d)
 /* ------------------------------------------------------------------------------------------ */
 /* k_gprop: update_G proposals (mcmc.c:1060-1084) and stream positions                          */
 /* ------------------------------------------------------------------------------------------ */
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_gprop(DevView d, const double *S, isg_wh base, int keyed, uint64_t *pos_out)
+template <int BLOCK, int KC>
+__device__ __forceinline__ void gprop_body(DevView d, const double *S, isg_wh base, int keyed, uint64_t *pos_out)
 {
 	__shared__ unsigned sm[BLOCK / 64 + 1];
-	__shared__ double Ssh[ISG_KCAP];
+	__shared__ double Ssh[KC];
 	const bool indiv = (d.mode == 3); /* mode 3: S has one selfing rate per individual (mcmc.c:1069-1070) */
 	if (!indiv && threadIdx.x < (unsigned)d.K) Ssh[threadIdx.x] = S[threadIdx.x];
 	__syncthreads();
@@ -435,51 +443,10 @@ __global__ void __launch_bounds__(BLOCK) k_gprop(DevView d, const double *S, isg
 	}
 	if (threadIdx.x == 0) *pos_out = (uint64_t)d.N + running;
 }
-/* K > ISG_KCAP: the same with the wide cap (a body shared with k_gprop through a template changed k_gprop's register allocation) */
 template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_gprop_w(DevView d, const double *S, isg_wh base, int keyed, uint64_t *pos_out)
-{
-	__shared__ unsigned sm[BLOCK / 64 + 1];
-	__shared__ double Ssh[ISG_KWIDE];
-	const bool indiv = (d.mode == 3); /* mode 3: S has one selfing rate per individual (mcmc.c:1069-1070) */
-	if (!indiv && threadIdx.x < (unsigned)d.K) Ssh[threadIdx.x] = S[threadIdx.x];
-	__syncthreads();
-	unsigned running = 0;
-	for (int i0 = 0; i0 < d.N; i0 += BLOCK) {
-		int i = i0 + threadIdx.x;
-		double selfing = 0;
-		int stat = 0;
-		if (i < d.N) {
-			if (indiv) selfing = S[i];
-			else for (int k = 0; k < d.K; k++) selfing += d.qq[(size_t)i * d.K + k] * Ssh[k];
-			stat = isg_dt_stat(selfing);
-			if (stat < 0) { /* mcmc.c:1540-1541: the reference prints the value and exits; the host does that after this launch */
-				if ((atomicOr(d.err, 2u) & 2u) == 0u) *(double *)(d.err + 2) = selfing; /* the first offender's value */
-				stat = 1;
-			}
-		}
-		unsigned flag = (i < d.N && stat == 1) ? 1u : 0u, tot, pre;
-		pre = block_excl_scan<BLOCK>(flag, sm, &tot);
-		if (i < d.N) {
-			uint64_t pos = keyed ? 2ull * (uint64_t)i : (uint64_t)i + running + pre;
-			isg_cursor c;
-			c.s = isg_wh_jump(d.tab, base, pos);
-			c.used = 0;
-			c.tape = nullptr;
-			int gen;
-			if (stat == 1) {
-				gen = isg_rgeom(&c, 1 - selfing);
-				if (gen < 1) gen = 1;
-				if (gen > 50) gen = 50;
-			} else if (stat == 0) gen = 1;
-			else gen = 50;
-			d.genprop[i] = gen;
-			d.uacc[i] = isg_cur_next(&c);
-		}
-		running += tot;
-	}
-	if (threadIdx.x == 0) *pos_out = (uint64_t)d.N + running;
-}
+__global__ void __launch_bounds__(BLOCK) k_gprop(DevView d, const double *S, isg_wh base, int keyed, uint64_t *pos_out) { gprop_body<BLOCK, ISG_KCAP>(d, S, base, keyed, pos_out); }
+template <int BLOCK> /* K > ISG_KCAP */
+__global__ void __launch_bounds__(BLOCK) k_gprop_w(DevView d, const double *S, isg_wh base, int keyed, uint64_t *pos_out) { gprop_body<BLOCK, ISG_KWIDE>(d, S, base, keyed, pos_out); }
 
 /* ------------------------------------------------------------------------------------------ */
 /* k_loglik: log_ld_indv (mcmc.c:1726-1773) for a proposal/current pair or for cal_lkh          */
@@ -3406,7 +3373,7 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	isg_ctx *c = new isg_ctx(); /* value-initialised: every pointer starts null */
 	c->cfg = *cfg;
 	ctx_count(c, +1);
-	{ const char *e_ = getenv("INSTRUCT_HOST_TIMING"); c->host_timing = e_ && atoi(e_) == 1; }
+	c->host_timing = env_flag(getenv("INSTRUCT_HOST_TIMING"), false);
 	memset(&c->d, 0, sizeof(c->d));
 	CtxGuard guard(c); /* any early return below releases what has been allocated so far */
 	const int N = cfg->N, L = cfg->L, K = cfg->K;
@@ -3458,13 +3425,11 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	d.lli = nullptr;
 	d.lli_F = 0;
 	if (cfg->type_freq == 1 || cfg->mode == 0) { /* (-y 0 mixes the frequencies with the individual's qq: no tables) */
-		const char *e = getenv("INSTRUCT_LL_TABLES");
-		if (!(e && atoi(e) == 0)) {
+		if (env_flag(getenv("INSTRUCT_LL_TABLES"), true)) {
 			DALLOC(d.lftab, double, (size_t)L * Amax * K);
 			const size_t ent = (size_t)50 * L * Amax * Amax * K;
-			const char *ei = getenv("INSTRUCT_LL_INT");
 			const size_t enti = 1 + (size_t)50 * Lp * Amax * Amax * K + (size_t)Lp * Amax * K; /* the integer form, locus innermost (k_loglik_int) */
-			if (cfg->mode == 2 && !(ei && atoi(ei) == 0) && enti * sizeof(int2) <= ((size_t)1 << 30)) {
+			if (cfg->mode == 2 && env_flag(getenv("INSTRUCT_LL_INT"), true) && enti * sizeof(int2) <= ((size_t)1 << 30)) {
 				DALLOC(d.lli, int2, enti);
 				d.lli_F = (unsigned)(1 + (size_t)50 * Lp * Amax * Amax * K);
 			} else if (cfg->mode == 2 && ent * sizeof(double) <= ((size_t)1 << 30)) { DALLOC(d.lltab, double, ent); } /* (mode 3: unclamped initial generations) */
@@ -3502,22 +3467,14 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 		CoopBuf *cbp;
 		DALLOC(cbp, CoopBuf, 1);
 		c->d_coop = cbp;
-		const char *e = getenv("INSTRUCT_ZQ_COOP");
-		c->coop = (e && atoi(e) == 0) ? 0 : 1;
-		e = getenv("INSTRUCT_ZQ_SPEC");
-		c->spec = (e && atoi(e) == 0) ? 0 : 1;
-		e = getenv("INSTRUCT_ZQ_XCD"); /* experimental, off by default: measured gain at config 3 is within noise */
-		c->xcd = (e && atoi(e) == 1) ? 1 : 0;
-		e = getenv("INSTRUCT_ZQ_PIPE");
-		c->pipe = (e && atoi(e) == 0) ? 0 : 1;
-		e = getenv("INSTRUCT_HOST_TAPE");
-		c->host_tape = (e && atoi(e) == 0) ? 0 : 1;
-		e = getenv("INSTRUCT_SPOP_TREE");
-		c->spop_tree = (e && atoi(e) == 0) ? 0 : 1;
-		e = getenv("INSTRUCT_ZQ_PIPE_XCD");
-		c->pipe_xcd = (e && atoi(e) == 0) ? 0 : 1;
-		e = getenv("INSTRUCT_ZQ_TEST_ABORT");
-		c->test_abort = e ? atoi(e) : 0;
+		c->coop = env_flag(getenv("INSTRUCT_ZQ_COOP"), true);
+		c->spec = env_flag(getenv("INSTRUCT_ZQ_SPEC"), true);
+		c->xcd = env_flag(getenv("INSTRUCT_ZQ_XCD"), false); /* experimental, off by default: measured gain at config 3 is within noise */
+		c->pipe = env_flag(getenv("INSTRUCT_ZQ_PIPE"), true);
+		c->host_tape = env_flag(getenv("INSTRUCT_HOST_TAPE"), true);
+		c->spop_tree = env_flag(getenv("INSTRUCT_SPOP_TREE"), true);
+		c->pipe_xcd = env_flag(getenv("INSTRUCT_ZQ_PIPE_XCD"), true);
+		c->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_TEST_ABORT"), 0);
 	}
 	DALLOC(d.cnt, int, (size_t)Lp * Amax * K);
 	DALLOC(d.qq, double, (size_t)N * K);
@@ -3959,6 +3916,54 @@ static bool coop_sweep_failed(isg_ctx *c, const unsigned flags[2])
 	if (c->test_abort > 0 && --c->test_abort == 0) bad = true;
 	return bad;
 }
+/* The uniforms base + 0 .. need - 1 of the stream as doubles in c->d_tape (which only grows), generated by the whole chip; the
+ * device view points at them. */
+static int tape_fill(isg_ctx *c, isg_wh base, uint64_t need)
+{
+	if (need > c->tape_cap) {
+		if (c->d_tape) HIPCHK(hipFree(c->d_tape));
+		c->d_tape = nullptr;
+		c->tape_cap = 0;
+		HIPCHK(hipMalloc((void **)&c->d_tape, sizeof(double) * need));
+		c->tape_cap = need;
+	}
+	if (need) {
+		prof_begin(c);
+		hipLaunchKernelGGL(k_tape, dim3((unsigned)((need + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, base, (unsigned long long)need, c->d_tape);
+		prof_end(c, "k_tape");
+	}
+	c->d.tape = c->d_tape;
+	c->d.tape_len = need;
+	return 0;
+}
+/* After a cooperative sweep's launch (qq saved in d_qqsave before it).  *done: the sweep completed and the stream is advanced; otherwise
+ * qq is back to its state before the sweep and the caller redoes it with the single-workgroup kernel (see coop_sweep_failed). */
+static int coop_sweep_end(isg_ctx *c, bool launched, bool *done)
+{
+	uint64_t used = 0;
+	unsigned flags[2] = {0, 0};
+	HIPCHK(hipMemcpyAsync(&used, c->d_pos, sizeof(used), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(flags, &((CoopBuf *)c->d_coop)->abort_flag, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	*done = launched && !coop_sweep_failed(c, flags);
+	if (*done) {
+		host_advance(c, used);
+		c->h_qq = false;
+		return 0;
+	}
+	HIPCHK(hipMemcpyAsync(c->d.qq, c->d_qqsave, sizeof(double) * (size_t)c->cfg.N * c->cfg.K, hipMemcpyDeviceToDevice, c->stream));
+	c->zq_fallbacks++;
+	return 0;
+}
+/* after the single-workgroup chain sweep (replay schedule): the stream moves on by what the sweep consumed */
+static int chain_sweep_end(isg_ctx *c)
+{
+	uint64_t used = 0;
+	HIPCHK(hipMemcpyAsync(&used, c->d_pos, sizeof(used), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	host_advance(c, used);
+	return 0;
+}
 template <int KMAX>
 static void launch_zq(isg_ctx *c, bool chain, isg_wh base, uint64_t pos0, uint64_t stride, int init_flag)
 {
@@ -3996,19 +4001,8 @@ extern "C" int isg_update_ZQ(isg_ctx *c, int init_flag)
 		 * individual boundaries fall, so they are generated up front by the whole chip; the serial
 		 * chain kernel then only reads them. */
 		uint64_t need = 2 * c->nvalid_total + (uint64_t)(8 * K + 32 > 96 ? 8 * K + 32 : 96) * (uint64_t)c->cfg.N + 4096;
-		if (need > c->tape_cap) {
-			if (c->d_tape) HIPCHK(hipFree(c->d_tape));
-			c->d_tape = nullptr;
-			c->tape_cap = 0;
-			HIPCHK(hipMalloc((void **)&c->d_tape, sizeof(double) * need));
-			c->tape_cap = need;
-		}
-		prof_begin(c);
-		hipLaunchKernelGGL(k_tape, dim3((unsigned)((need + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, base, (unsigned long long)need, c->d_tape);
-		prof_end(c, "k_tape");
+		if (tape_fill(c, base, need)) return 1;
 		HIPCHK(hipGetLastError());
-		c->d.tape = c->d_tape;
-		c->d.tape_len = need;
 	}
 	const bool coop = chain && c->coop && K <= ISG_KCAP; /* K > ISG_KCAP: the chain form of the wide k_zq */
 	if (coop) {
@@ -4037,81 +4031,39 @@ extern "C" int isg_update_ZQ(isg_ctx *c, int init_flag)
 		HIPCHK(hipMemcpyAsync(c->d_qqsave, c->d.qq, sizeof(double) * (size_t)c->cfg.N * K, hipMemcpyDeviceToDevice, c->stream));
 		bool launched = true;
 		prof_begin(c);
-#define COOP_LAUNCH(KM) do { if (fits_resident(k_zq_coop<KM>, 256, G, c->cfg.device)) hipLaunchKernelGGL((k_zq_coop<KM>), dim3(pack ? 8 * G : G), dim3(256), 0, c->stream, c->d, base, init_flag, c->alpha, cb, c->d_pos, pack); else launched = false; } while (0)
-#define SPEC_LAUNCH(KM) do { if (fits_resident(k_zq_spec<KM>, 256, G, c->cfg.device)) hipLaunchKernelGGL((k_zq_spec<KM>), dim3(pack ? 8 * G : G), dim3(256), 0, c->stream, c->d, base, c->alpha, cb, c->d_pos, pack); else launched = false; } while (0)
-#define PIPE_LAUNCH(KM) do { if (fits_resident(k_zq_pipe<KM, ISG_PIPE_DW>, 64 * (ISG_PIPE_DW + 1), GP, c->cfg.device)) hipLaunchKernelGGL((k_zq_pipe<KM, ISG_PIPE_DW>), dim3(ppack ? 8 * GP : GP), dim3(64 * (ISG_PIPE_DW + 1)), 0, c->stream, c->d, base, c->alpha, cb, c->d_pipe, c->d_pos, ppack); else launched = false; } while (0)
-		if (pipe) {
-			switch (K) {
-			case 1: case 2: PIPE_LAUNCH(2); break;
-			case 3: PIPE_LAUNCH(3); break;
-			case 4: PIPE_LAUNCH(4); break;
-			case 5: PIPE_LAUNCH(5); break;
-			case 6: PIPE_LAUNCH(6); break;
-			default: PIPE_LAUNCH(8); break;
-			}
-		} else if (spec) {
-			switch (K) {
-			case 1: case 2: SPEC_LAUNCH(2); break;
-			case 3: SPEC_LAUNCH(3); break;
-			case 4: SPEC_LAUNCH(4); break;
-			case 5: SPEC_LAUNCH(5); break;
-			case 6: SPEC_LAUNCH(6); break;
-			default: SPEC_LAUNCH(8); break;
-			}
-		} else
-		switch (K) {
-		case 1: case 2: COOP_LAUNCH(2); break;
-		case 3: COOP_LAUNCH(3); break;
-		case 4: COOP_LAUNCH(4); break;
-		case 5: COOP_LAUNCH(5); break;
-		case 6: COOP_LAUNCH(6); break;
-		case 7: case 8: COOP_LAUNCH(8); break;
-		default:
-			if (K <= 12) COOP_LAUNCH(12);
-			else if (K <= 16) COOP_LAUNCH(16);
-			else if (K <= 24) COOP_LAUNCH(24);
-			else COOP_LAUNCH(32);
-		}
-#undef COOP_LAUNCH
+		if (pipe)
+			kdispatch(KL_ZQ_8(), K, [&](auto km) {
+				constexpr int KM = decltype(km)::value;
+				if (fits_resident(k_zq_pipe<KM, ISG_PIPE_DW>, 64 * (ISG_PIPE_DW + 1), GP, c->cfg.device))
+					hipLaunchKernelGGL((k_zq_pipe<KM, ISG_PIPE_DW>), dim3(ppack ? 8 * GP : GP), dim3(64 * (ISG_PIPE_DW + 1)), 0, c->stream, c->d, base, c->alpha, cb, c->d_pipe, c->d_pos, ppack);
+				else launched = false;
+			});
+		else if (spec)
+			kdispatch(KL_ZQ_8(), K, [&](auto km) {
+				constexpr int KM = decltype(km)::value;
+				if (fits_resident(k_zq_spec<KM>, 256, G, c->cfg.device))
+					hipLaunchKernelGGL((k_zq_spec<KM>), dim3(pack ? 8 * G : G), dim3(256), 0, c->stream, c->d, base, c->alpha, cb, c->d_pos, pack);
+				else launched = false;
+			});
+		else
+			kdispatch(KL_ZQ_COOP(), K, [&](auto km) {
+				constexpr int KM = decltype(km)::value;
+				if (fits_resident(k_zq_coop<KM>, 256, G, c->cfg.device))
+					hipLaunchKernelGGL((k_zq_coop<KM>), dim3(pack ? 8 * G : G), dim3(256), 0, c->stream, c->d, base, init_flag, c->alpha, cb, c->d_pos, pack);
+				else launched = false;
+			});
 		prof_end(c, pipe ? "k_zq_pipe" : spec ? "k_zq_spec" : "k_zq_coop");
 		HIPCHK(hipGetLastError());
-		uint64_t used = 0;
-		unsigned flags[2] = {0, 0};
-		HIPCHK(hipMemcpyAsync(&used, c->d_pos, sizeof(used), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipMemcpyAsync(flags, &cb->abort_flag, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (launched && !coop_sweep_failed(c, flags)) {
-			host_advance(c, used);
-			c->h_qq = false;
-			return 0;
-		}
-		/* redo with the single-workgroup kernel below (see coop_sweep_failed) */
-		HIPCHK(hipMemcpyAsync(c->d.qq, c->d_qqsave, sizeof(double) * (size_t)c->cfg.N * K, hipMemcpyDeviceToDevice, c->stream));
-		c->zq_fallbacks++;
+		bool done = false;
+		if (coop_sweep_end(c, launched, &done)) return 1;
+		if (done) return 0;
 	}
 	prof_begin(c);
-	switch (K) { /* small K: exact-size register arrays; larger K: rounded up */
-	case 1: case 2: launch_zq<2>(c, chain, base, pos0, stride, init_flag); break;
-	case 3: launch_zq<3>(c, chain, base, pos0, stride, init_flag); break;
-	case 4: launch_zq<4>(c, chain, base, pos0, stride, init_flag); break;
-	case 5: launch_zq<5>(c, chain, base, pos0, stride, init_flag); break;
-	case 6: launch_zq<6>(c, chain, base, pos0, stride, init_flag); break;
-	case 7: case 8: launch_zq<8>(c, chain, base, pos0, stride, init_flag); break;
-	default:
-		if (K <= 12) launch_zq<12>(c, chain, base, pos0, stride, init_flag);
-		else if (K <= 16) launch_zq<16>(c, chain, base, pos0, stride, init_flag);
-		else if (K <= 24) launch_zq<24>(c, chain, base, pos0, stride, init_flag);
-		else if (K <= ISG_KCAP) launch_zq<32>(c, chain, base, pos0, stride, init_flag);
-		else launch_zq<ISG_KWIDE>(c, chain, base, pos0, stride, init_flag); /* K-generic wide kernels (zq_one, K > ISG_KCAP) */
-	}
+	/* small K: exact-size register arrays; larger K: rounded up; K > ISG_KCAP: the K-generic wide kernels (zq_one) */
+	kdispatch(KL_ZQ(), K, [&](auto km) { launch_zq<decltype(km)::value>(c, chain, base, pos0, stride, init_flag); });
 	prof_end(c, chain ? "k_zq_chain" : "k_zq_keyed");
 	HIPCHK(hipGetLastError());
-	if (chain) {
-		uint64_t used = 0;
-		HIPCHK(hipMemcpyAsync(&used, c->d_pos, sizeof(used), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		host_advance(c, used);
-	}
+	if (chain && chain_sweep_end(c)) return 1;
 	c->h_qq = false;
 	return 0;
 }

@@ -388,8 +388,9 @@ __device__ __forceinline__ void geno_one(const PolyDev &p, const isg_wh &base, i
  * individual re-streams the tables from the memory side: 23 GB per sweep at config 5).
  * One wave = 64 consecutive loci of ONE individual (the stream rank of a locus is a ballot prefix).
  */
-/* ALLO: the allotetraploid genotype draw (a template parameter: the autotetraploid kernel does not carry its registers) */
-template <int KMAX, bool ALLO>
+/* ALLO: the allotetraploid genotype draw (a template parameter: the autotetraploid kernel does not carry its registers).
+ * WIDE: the autotetraploid draw of a wide-allele context (the allotetraploid draw has closed-form rows already: ALLO && WIDE is not used) */
+template <int KMAX, bool ALLO, bool WIDE = false>
 __global__ void __launch_bounds__(256) k4_geno(PolyDev p, isg_wh base, int init, const double *tape, int chunk, int nchunk)
 {
 	const int b = (int)blockIdx.x, r = b >> 3;
@@ -401,22 +402,7 @@ __global__ void __launch_bounds__(256) k4_geno(PolyDev p, isg_wh base, int init,
 #pragma unroll
 		for (int m = 0; m < KMAX; m++) qf[m] = (m < p.K && !init) ? (float)p.qq[(size_t)i * p.K + m] : 0.f;
 		if (ALLO) geno_one_allo(p, base, init, tape, i, j);
-		else geno_one<KMAX, false>(p, base, init, tape, i, j, qf);
-	}
-}
-/* the autotetraploid draw of a wide-allele context (the allotetraploid draw has closed-form rows already: k4_geno<KMAX, true>) */
-template <int KMAX>
-__global__ void __launch_bounds__(256) k4_geno_w(PolyDev p, isg_wh base, int init, const double *tape, int chunk, int nchunk)
-{
-	const int b = (int)blockIdx.x, r = b >> 3;
-	const int tile = (r / nchunk) * 8 + (b & 7), ch = r % nchunk;
-	const int j = tile * 256 + (int)threadIdx.x, i0 = ch * chunk, i1 = min(p.N, i0 + chunk);
-	if (tile * 256 >= p.Lp) return;
-	for (int i = i0; i < i1; i++) {
-		float qf[KMAX];
-#pragma unroll
-		for (int m = 0; m < KMAX; m++) qf[m] = (m < p.K && !init) ? (float)p.qq[(size_t)i * p.K + m] : 0.f;
-		geno_one<KMAX, true>(p, base, init, tape, i, j, qf);
+		else geno_one<KMAX, WIDE>(p, base, init, tape, i, j, qf);
 	}
 }
 
@@ -431,7 +417,8 @@ __global__ void __launch_bounds__(256) k4_geno_w(PolyDev p, isg_wh base, int ini
  * A workgroup takes 64 loci (one wave = 256 contiguous bytes of a row) x a chunk of individuals and keeps both
  * allele count tiles in LDS ([allele][cluster][locus]: lanes of a wave hit distinct banks).
  */
-template <bool TILE, bool ALLO>
+/* WIDE: a wide-allele context, where same-cluster loci find their row in closed form */
+template <bool TILE, bool ALLO, bool WIDE>
 __global__ void __launch_bounds__(256) k4_sweep_counts(PolyDev p, int chunk, int *cntmix, unsigned long long *catcnt)
 {
 	extern __shared__ int tile[]; /* [2][Amax * K][64] */
@@ -465,74 +452,7 @@ __global__ void __launch_bounds__(256) k4_sweep_counts(PolyDev p, int chunk, int
 			}
 			const unsigned g0 = g & 0xff, g1 = (g >> 8) & 0xff, g2 = (g >> 16) & 0xff, g3 = g >> 24;
 			if (same) {
-				atomicAdd(&p.ccnt[((size_t)(z & 0xff) * p.L + j) * p.GS + poly_gid(p, j, g0, g1, g2, g3)], 1);
-			} else if (ALLO) { /* get_cat_allo (poly_geno.c:1341-1372) */
-				ncat[(g0 != g1 ? 2 : 0) + (g2 != g3 ? 1 : 0)]++;
-			} else {
-				/* get_cat_auto (poly_geno.c:1313-1339): distinct alleles; two of them: 2+2 or 3+1 */
-				const int nd = 1 + (g1 != g0) + (g2 != g0 && g2 != g1) + (g3 != g0 && g3 != g1 && g3 != g2);
-				const int m0 = 1 + (g1 == g0) + (g2 == g0) + (g3 == g0);
-				ncat[nd == 1 ? 0 : nd == 2 ? (m0 == 2 ? 2 : 1) : nd]++;
-			}
-		}
-	}
-	if (TILE) {
-		__syncthreads();
-		for (int e = threadIdx.x; e < 2 * AK * 64; e += 256) {
-			const int v = tile[e];
-			const int l = e & 63, r = e >> 6, jj = blockIdx.x * 64 + l;
-			if (v && jj < p.L) {
-				if (r < AK) atomicAdd(&p.cnt[(size_t)jj * AK + r], v);
-				else atomicAdd(&cntmix[(size_t)jj * AK + (r - AK)], v);
-			}
-		}
-	}
-#pragma unroll
-	for (int q = 1; q < 5; q++) {
-		unsigned v = ncat[q];
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-		if (lane == 0 && v) atomicAdd(&catcnt[q], (unsigned long long)v);
-	}
-}
-
-/* the same sweep in a wide-allele context: same-cluster loci find their row in closed form.  (A copy rather than a shared body: with the
- * body in a function the existing kernel compiled to one more SGPR.) */
-template <bool TILE, bool ALLO>
-__global__ void __launch_bounds__(256) k4_sweep_counts_w(PolyDev p, int chunk, int *cntmix, unsigned long long *catcnt)
-{
-	extern __shared__ int tile[]; /* [2][Amax * K][64] */
-	const int AK = p.Amax * p.K, lane = (int)lane_id(), wave = threadIdx.x >> 6;
-	const int j = blockIdx.x * 64 + lane, i0 = blockIdx.y * chunk, i1 = min(p.N, i0 + chunk);
-	if (TILE) {
-		for (int e = threadIdx.x; e < 2 * AK * 64; e += 256) tile[e] = 0;
-		__syncthreads();
-	}
-	unsigned ncat[5] = {0, 0, 0, 0, 0};
-	if (j < p.L) {
-		for (int i = i0 + wave; i < i1; i += 4) {
-			const size_t id = (size_t)i * p.Lp + j;
-			const unsigned g = *(const unsigned *)(p.geno + id * 4);
-			if ((g & 0xff) == 0xff) continue;
-			const unsigned z = *(const unsigned *)(p.z + id * 4);
-			const bool same = (z == (z & 0xff) * 0x01010101u);
-#pragma unroll
-			for (int c = 0; c < 4; c++) {
-				const int a = (g >> (8 * c)) & 0xff, k = (z >> (8 * c)) & 0xff;
-				if (TILE) {
-					atomicAdd(&tile[(a * p.K + k) * 64 + lane], 1);
-					if (!same) atomicAdd(&tile[(AK + a * p.K + k) * 64 + lane], 1);
-				} else if (ALLO && c >= 2) { /* the second subgenome's copies (seqpop2, poly_geno.c:481-492) */
-					atomicAdd(&p.cnt2[((size_t)j * p.Amax + a) * p.K + k], 1);
-					if (!same) atomicAdd(&p.cntmix2[((size_t)j * p.Amax + a) * p.K + k], 1);
-				} else {
-					atomicAdd(&p.cnt[((size_t)j * p.Amax + a) * p.K + k], 1);
-					if (!same) atomicAdd(&cntmix[((size_t)j * p.Amax + a) * p.K + k], 1);
-				}
-			}
-			const unsigned g0 = g & 0xff, g1 = (g >> 8) & 0xff, g2 = (g >> 16) & 0xff, g3 = g >> 24;
-			if (same) {
-				atomicAdd(&p.ccnt[((size_t)(z & 0xff) * p.L + j) * p.GS + poly_row_w<ALLO>(p, j, g0, g1, g2, g3)], 1);
+				atomicAdd(&p.ccnt[((size_t)(z & 0xff) * p.L + j) * p.GS + (WIDE ? poly_row_w<ALLO>(p, j, g0, g1, g2, g3) : poly_gid(p, j, g0, g1, g2, g3))], 1);
 			} else if (ALLO) { /* get_cat_allo (poly_geno.c:1341-1372) */
 				ncat[(g0 != g1 ? 2 : 0) + (g2 != g3 ? 1 : 0)]++;
 			} else {
@@ -1699,10 +1619,8 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 		CoopBuf *cbp;
 		DALLOC(cbp, CoopBuf, 1);
 		c->d_coop = cbp;
-		const char *e = getenv("INSTRUCT_ZQ_COOP");
-		c->coop = (e && atoi(e) == 0) ? 0 : 1;
-		e = getenv("INSTRUCT_ZQ_TEST_ABORT");
-		c->test_abort = e ? atoi(e) : 0;
+		c->coop = env_flag(getenv("INSTRUCT_ZQ_COOP"), true);
+		c->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_TEST_ABORT"), 0);
 	}
 	c->d_tape = nullptr;
 	c->tape_cap = 0;
@@ -1711,8 +1629,7 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 	{ /* replay update_ZQ with the start positions resolved block-wise (k4_zq_block): opt-in for ploidy 4.  A candidate costs
 	   * 4 L draws against K - 1 thresholds and the windows widen with K: at config 5 (K = 10, L = 20000) the resolution takes
 	   * 158 ms + 8.6 ms for the sweep, the cooperative chain kernel 105 ms (INSTRUCT_ZQ_RESOLVE_P4=1 to use it anyway) */
-		const char *e = getenv("INSTRUCT_ZQ_RESOLVE_P4");
-		if (e && atoi(e) == 1 && resolve_alloc(c, nvalid, 4, 16)) return 1;
+		if (env_flag(getenv("INSTRUCT_ZQ_RESOLVE_P4"), false) && resolve_alloc(c, nvalid, 4, 16)) return 1;
 		if (c->rs) c->rs->err_bit = 8u;
 	}
 	if (cfg->rng_sched == ISG_SCHED_REPLAY) {
@@ -1799,37 +1716,17 @@ static int poly_geno_sweep(isg_ctx *c, int init)
 	/* the sweep's uniforms in stream order, generated 8 per lane (one skip-ahead per 8 instead of one per draw) */
 	const uint64_t need = c->poly->total_amb;
 	const isg_wh gbase = is_keyed(c) ? isg_wh_jump(&c->tab_h, c->origin, init ? 1 : iter_base(c) + c->ky[KY_OFFG]) : c->rng;
-	if (need > c->tape_cap) {
-		if (c->d_tape) HIPCHK(hipFree(c->d_tape));
-		c->d_tape = nullptr;
-		c->tape_cap = 0;
-		HIPCHK(hipMalloc((void **)&c->d_tape, sizeof(double) * need));
-		c->tape_cap = need;
-	}
-	if (need) {
-		prof_begin(c);
-		hipLaunchKernelGGL(k_tape, dim3((unsigned)((need + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, gbase, (unsigned long long)need, c->d_tape);
-		prof_end(c, "k_tape");
-	}
+	if (tape_fill(c, gbase, need)) return 1; /* (nothing to fill: no launch) */
 	prof_begin(c);
 	const int gchunk = p.N >= 2048 ? 256 : (p.N + 7) / 8, nchunk = (p.N + gchunk - 1) / gchunk, ntile = (p.Lp + 255) / 256;
 	const dim3 ggrid((unsigned)(((ntile + 7) / 8) * 8 * nchunk));
-#define GENO_LAUNCH(KM) do { if (p.allo) hipLaunchKernelGGL((k4_geno<KM, true>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk); \
-	else hipLaunchKernelGGL((k4_geno<KM, false>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk); } while (0)
-	if (c->poly->wide && !p.allo) {
-#define GENO_W(KM) hipLaunchKernelGGL((k4_geno_w<KM>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk)
-		if (p.K <= 4) GENO_W(4);
-		else if (p.K <= 8) GENO_W(8);
-		else if (p.K <= 12) GENO_W(12);
-		else if (p.K <= 16) GENO_W(16);
-		else GENO_W(32);
-#undef GENO_W
-	} else if (p.K <= 4) GENO_LAUNCH(4);
-	else if (p.K <= 8) GENO_LAUNCH(8);
-	else if (p.K <= 12) GENO_LAUNCH(12);
-	else if (p.K <= 16) GENO_LAUNCH(16);
-	else GENO_LAUNCH(32);
-#undef GENO_LAUNCH
+	const bool wide = c->poly->wide;
+	kdispatch(KL_P4_GENO(), p.K, [&](auto km) {
+		constexpr int KM = decltype(km)::value;
+		if (p.allo) hipLaunchKernelGGL((k4_geno<KM, true>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk);
+		else if (wide) hipLaunchKernelGGL((k4_geno<KM, false, true>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk);
+		else hipLaunchKernelGGL((k4_geno<KM, false>), ggrid, dim3(256), 0, c->stream, p, gbase, init, (const double *)c->d_tape, gchunk, nchunk);
+	});
 	prof_end(c, init ? "k4_geno_init" : "k4_geno");
 	HIPCHK(hipGetLastError());
 	/* one uniform per locus with 2 or 3 distinct alleles: the consumption is a property of the data */
@@ -1857,12 +1754,12 @@ static int poly_sweep_counts(isg_ctx *c)
 	const dim3 grid((L + 63) / 64, (p.N + chunk - 1) / chunk);
 	prof_begin(c);
 	if (pc->wide) {
-		if (p.allo) hipLaunchKernelGGL((k4_sweep_counts_w<false, true>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
-		else if (lds <= 60000) hipLaunchKernelGGL((k4_sweep_counts_w<true, false>), grid, dim3(256), lds, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
-		else hipLaunchKernelGGL((k4_sweep_counts_w<false, false>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
-	} else if (p.allo) hipLaunchKernelGGL((k4_sweep_counts<false, true>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
-	else if (lds <= 60000) hipLaunchKernelGGL((k4_sweep_counts<true, false>), grid, dim3(256), lds, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
-	else hipLaunchKernelGGL((k4_sweep_counts<false, false>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+		if (p.allo) hipLaunchKernelGGL((k4_sweep_counts<false, true, true>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+		else if (lds <= 60000) hipLaunchKernelGGL((k4_sweep_counts<true, false, true>), grid, dim3(256), lds, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+		else hipLaunchKernelGGL((k4_sweep_counts<false, false, true>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+	} else if (p.allo) hipLaunchKernelGGL((k4_sweep_counts<false, true, false>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+	else if (lds <= 60000) hipLaunchKernelGGL((k4_sweep_counts<true, false, false>), grid, dim3(256), lds, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
+	else hipLaunchKernelGGL((k4_sweep_counts<false, false, false>), grid, dim3(256), 0, c->stream, p, chunk, pc->d_cntmix, pc->d_catcnt);
 	prof_end(c, "k4_sweep_counts");
 	HIPCHK(hipGetLastError());
 	pc->counts_valid = true;
@@ -2140,103 +2037,78 @@ static int poly_update_ZQ(isg_ctx *c, int init_flag)
 		SpecCtx *sp = c->zspec;
 		const isg_wh base = c->rng;
 		const bool zold = sp->zstrip; /* INSTRUCT_ZEXPECT_STRIP=1: the strip-per-wave kernel (k4_zexpect) instead of one lane per individual */
-#define P4S_DISPATCH(CALL) do { if (K <= 2) CALL(2); else if (K <= 4) CALL(4); else if (K <= 6) CALL(6); else if (K <= 8) CALL(8); else if (K <= 12) CALL(12); else if (K <= 16) CALL(16); else if (K <= 24) CALL(24); else CALL(32); } while (0)
-#define P4S_MI(KM) ((KM) <= 8 ? 4 : (KM) <= 12 ? 3 : (KM) <= 16 ? 2 : 1) /* individuals per workgroup: 2 MI KM accumulators + MI KM weights per lane */
-#define P4S_EXPECT(KM) do { const unsigned zg = 8u * (unsigned)((c->cfg.N + P4S_MI(KM) - 1) / P4S_MI(KM)); int zr = 8; \
-	if (c->poly->p.Amax * c->d.KPF <= K4Z_SCR_FLOATS && !zold) { zr = (c->cfg.L + 63) / 64 < K4Z_NRANGE ? (c->cfg.L + 63) / 64 : K4Z_NRANGE; \
-		hipLaunchKernelGGL((k4_zexpect_ind<KM>), dim3((unsigned)((c->cfg.N + 255) / 256) * (unsigned)zr), dim3(256), 0, c->stream, c->poly->p, c->d, c->poly->d_zpart, zr); } \
-	else if (c->poly->p.Amax * c->d.KPF <= K4Z_SCR_FLOATS) hipLaunchKernelGGL((k4_zexpect<KM, true, P4S_MI(KM)>), dim3(zg), dim3(256), 0, c->stream, c->poly->p, c->d, c->poly->d_zpart); \
-	else hipLaunchKernelGGL((k4_zexpect<KM, false, P4S_MI(KM)>), dim3(zg), dim3(256), 0, c->stream, c->poly->p, c->d, c->poly->d_zpart); \
-	hipLaunchKernelGGL(k4_zexpect_fin, dim3((unsigned)((c->cfg.N * K + 255) / 256)), dim3(256), 0, c->stream, c->poly->p, (const float *)c->poly->d_zpart, c->alpha, sp->ksig, alo, ahi, zr); } while (0)
-#define P4S_PROBE(KM) hipLaunchKernelGGL((k4_zq_probe<256, KM>), dim3(grid), dim3(256), 0, c->stream, c->poly->p, c->d, base, c->alpha, (const unsigned long long *)sp->d_B, (const SpecProbe *)sp->d_list, \
-					 sp->d_dev, sp->list_cap, sp->walk.d_table)
-#define P4S_AT(KM) hipLaunchKernelGGL((k4_zq<256, KM, false>), dim3(c->cfg.N), dim3(256), 0, c->stream, c->poly->p, c->d, base, (uint64_t)0, (uint64_t)0, 0, c->alpha, c->d_pos, \
-				      (const unsigned long long *)sp->d_offs, (const ResolveState *)sp->d_rs)
-		if (spec_update_ZQ_with(c, sp, base, &done, [&](float *alo, float *ahi) { P4S_DISPATCH(P4S_EXPECT); }, [&](int grid) { P4S_DISPATCH(P4S_PROBE); }, [&]() { P4S_DISPATCH(P4S_AT); })) return 1;
-#undef P4S_EXPECT
-#undef P4S_MI
-#undef P4S_PROBE
-#undef P4S_AT
-#undef P4S_DISPATCH
+		auto expect = [&](float *alo, float *ahi) {
+			kdispatch(KL_P4(), K, [&](auto km) {
+				constexpr int KM = decltype(km)::value;
+				constexpr int MI = KM <= 8 ? 4 : KM <= 12 ? 3 : KM <= 16 ? 2 : 1; /* individuals per workgroup: 2 MI KM accumulators + MI KM weights per lane */
+				const unsigned zg = 8u * (unsigned)((c->cfg.N + MI - 1) / MI);
+				int zr = 8;
+				if (c->poly->p.Amax * c->d.KPF <= K4Z_SCR_FLOATS && !zold) {
+					zr = (c->cfg.L + 63) / 64 < K4Z_NRANGE ? (c->cfg.L + 63) / 64 : K4Z_NRANGE;
+					hipLaunchKernelGGL((k4_zexpect_ind<KM>), dim3((unsigned)((c->cfg.N + 255) / 256) * (unsigned)zr), dim3(256), 0, c->stream, c->poly->p, c->d, c->poly->d_zpart, zr);
+				} else if (c->poly->p.Amax * c->d.KPF <= K4Z_SCR_FLOATS)
+					hipLaunchKernelGGL((k4_zexpect<KM, true, MI>), dim3(zg), dim3(256), 0, c->stream, c->poly->p, c->d, c->poly->d_zpart);
+				else
+					hipLaunchKernelGGL((k4_zexpect<KM, false, MI>), dim3(zg), dim3(256), 0, c->stream, c->poly->p, c->d, c->poly->d_zpart);
+				hipLaunchKernelGGL(k4_zexpect_fin, dim3((unsigned)((c->cfg.N * K + 255) / 256)), dim3(256), 0, c->stream, c->poly->p, (const float *)c->poly->d_zpart, c->alpha, sp->ksig, alo, ahi, zr);
+			});
+		};
+		auto probe = [&](int grid) {
+			kdispatch(KL_P4(), K, [&](auto km) {
+				hipLaunchKernelGGL((k4_zq_probe<256, decltype(km)::value>), dim3(grid), dim3(256), 0, c->stream, c->poly->p, c->d, base, c->alpha, (const unsigned long long *)sp->d_B,
+						   (const SpecProbe *)sp->d_list, sp->d_dev, sp->list_cap, sp->walk.d_table);
+			});
+		};
+		auto at = [&]() {
+			kdispatch(KL_P4(), K, [&](auto km) {
+				hipLaunchKernelGGL((k4_zq<256, decltype(km)::value, false>), dim3(c->cfg.N), dim3(256), 0, c->stream, c->poly->p, c->d, base, (uint64_t)0, (uint64_t)0, 0, c->alpha, c->d_pos,
+						   (const unsigned long long *)sp->d_offs, (const ResolveState *)sp->d_rs);
+			});
+		};
+		if (spec_update_ZQ_with(c, sp, base, &done, expect, probe, at)) return 1;
 		if (done) return 0;
 	}
 	if (c->rs && !is_keyed(c) && !init_flag) { /* start positions resolved block-wise, then one parallel sweep (isg_resolve_hip.inc) */
 		bool done = false;
 		ResolveCtx *r = c->rs;
 		const isg_wh base = c->rng;
-#define P4_BLOCK(KM) hipLaunchKernelGGL((k4_zq_block<KM>), dim3(r->plan_h.nunits), dim3(256), 0, c->stream, c->poly->p, c->d, base, c->alpha, (const ResolvePlan *)r->d_plan, \
-					 r->d_st, (const unsigned long long *)r->d_B, (const float *)r->d_tapef, (unsigned long long)tl, r->d_offs, b)
-#define P4_AT(KM) hipLaunchKernelGGL((k4_zq<256, KM, false>), dim3(c->cfg.N), dim3(256), 0, c->stream, c->poly->p, c->d, base, (uint64_t)0, (uint64_t)0, 0, c->alpha, c->d_pos, \
-				     (const unsigned long long *)r->d_offs, (const ResolveState *)r->d_st)
-#define P4_DISPATCH(CALL) do { if (K <= 2) CALL(2); else if (K <= 4) CALL(4); else if (K <= 6) CALL(6); else if (K <= 8) CALL(8); else if (K <= 12) CALL(12); else CALL(16); } while (0)
-		if (resolve_update_ZQ_with(c, base, &done, [&](int b, uint64_t tl) { P4_DISPATCH(P4_BLOCK); }, [&]() { P4_DISPATCH(P4_AT); }, [&](uint64_t) { return false; })) return 1;
-#undef P4_BLOCK
-#undef P4_AT
-#undef P4_DISPATCH
+		auto block = [&](int b, uint64_t tl) {
+			kdispatch(KL_P4_BLOCK(), K, [&](auto km) {
+				hipLaunchKernelGGL((k4_zq_block<decltype(km)::value>), dim3(r->plan_h.nunits), dim3(256), 0, c->stream, c->poly->p, c->d, base, c->alpha, (const ResolvePlan *)r->d_plan,
+						   r->d_st, (const unsigned long long *)r->d_B, (const float *)r->d_tapef, (unsigned long long)tl, r->d_offs, b);
+			});
+		};
+		auto at = [&]() {
+			kdispatch(KL_P4_BLOCK(), K, [&](auto km) {
+				hipLaunchKernelGGL((k4_zq<256, decltype(km)::value, false>), dim3(c->cfg.N), dim3(256), 0, c->stream, c->poly->p, c->d, base, (uint64_t)0, (uint64_t)0, 0, c->alpha, c->d_pos,
+						   (const unsigned long long *)r->d_offs, (const ResolveState *)r->d_st);
+			});
+		};
+		if (resolve_update_ZQ_with(c, base, &done, block, at, [&](uint64_t) { return false; })) return 1;
 		if (done) return 0;
 	}
 	if (c->coop && !is_keyed(c)) {
 		/* the phase's stretch of the stream, generated by the whole chip (see isg_update_ZQ) */
 		const uint64_t need = 4 * c->nvalid_total + (16ull * K + 64) * (uint64_t)c->cfg.N + 8192;
-		if (need > c->tape_cap) {
-			if (c->d_tape) HIPCHK(hipFree(c->d_tape));
-			c->d_tape = nullptr;
-			c->tape_cap = 0;
-			HIPCHK(hipMalloc((void **)&c->d_tape, sizeof(double) * need));
-			c->tape_cap = need;
-		}
-		prof_begin(c);
-		hipLaunchKernelGGL(k_tape, dim3((unsigned)((need + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, c->rng, (unsigned long long)need, c->d_tape);
-		prof_end(c, "k_tape");
-		c->d.tape = c->d_tape;
-		c->d.tape_len = need;
+		if (tape_fill(c, c->rng, need)) return 1;
 		HIPCHK(hipMemsetAsync(c->d_coop, 0, sizeof(CoopBuf), c->stream));
 		int G = (c->poly->p.Lp + ISG_POLY_COOP_BLOCK - 1) / ISG_POLY_COOP_BLOCK;
 		if (G > ISG_COOP_GMAX) G = ISG_COOP_GMAX;
 		HIPCHK(hipMemcpyAsync(c->d_qqsave, c->d.qq, sizeof(double) * (size_t)c->cfg.N * K, hipMemcpyDeviceToDevice, c->stream));
-		bool launched;
+		bool launched = false;
 		prof_begin(c);
-		if (K <= 2) launched = poly_launch_zq_coop<2>(c, init_flag, G);
-		else if (K <= 4) launched = poly_launch_zq_coop<4>(c, init_flag, G);
-		else if (K <= 6) launched = poly_launch_zq_coop<6>(c, init_flag, G);
-		else if (K <= 8) launched = poly_launch_zq_coop<8>(c, init_flag, G);
-		else if (K <= 12) launched = poly_launch_zq_coop<12>(c, init_flag, G);
-		else if (K <= 16) launched = poly_launch_zq_coop<16>(c, init_flag, G);
-		else if (K <= 24) launched = poly_launch_zq_coop<24>(c, init_flag, G);
-		else launched = poly_launch_zq_coop<32>(c, init_flag, G);
+		kdispatch(KL_P4(), K, [&](auto km) { launched = poly_launch_zq_coop<decltype(km)::value>(c, init_flag, G); });
 		prof_end(c, "k4_zq_coop");
 		HIPCHK(hipGetLastError());
-		uint64_t used = 0;
-		unsigned flags[2] = {0, 0};
-		HIPCHK(hipMemcpyAsync(&used, c->d_pos, sizeof(used), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipMemcpyAsync(flags, &((CoopBuf *)c->d_coop)->abort_flag, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (launched && !coop_sweep_failed(c, flags)) {
-			host_advance(c, used);
-			c->h_qq = false;
-			return 0;
-		}
-		/* not completed: qq back to its state before the sweep, then the single-workgroup kernel (see coop_sweep_failed) */
-		HIPCHK(hipMemcpyAsync(c->d.qq, c->d_qqsave, sizeof(double) * (size_t)c->cfg.N * K, hipMemcpyDeviceToDevice, c->stream));
-		c->zq_fallbacks++;
+		bool done = false;
+		if (coop_sweep_end(c, launched, &done)) return 1;
+		if (done) return 0;
 	}
 	prof_begin(c);
-	if (K <= 2) poly_launch_zq<2>(c, init_flag);
-	else if (K <= 4) poly_launch_zq<4>(c, init_flag);
-	else if (K <= 6) poly_launch_zq<6>(c, init_flag);
-	else if (K <= 8) poly_launch_zq<8>(c, init_flag);
-	else if (K <= 12) poly_launch_zq<12>(c, init_flag);
-	else if (K <= 16) poly_launch_zq<16>(c, init_flag);
-	else if (K <= 24) poly_launch_zq<24>(c, init_flag);
-	else poly_launch_zq<32>(c, init_flag);
+	kdispatch(KL_P4(), K, [&](auto km) { poly_launch_zq<decltype(km)::value>(c, init_flag); });
 	prof_end(c, is_keyed(c) ? "k4_zq_keyed" : "k4_zq");
 	HIPCHK(hipGetLastError());
-	if (!is_keyed(c)) {
-		uint64_t used = 0;
-		HIPCHK(hipMemcpyAsync(&used, c->d_pos, sizeof(used), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		host_advance(c, used);
-	}
+	if (!is_keyed(c) && chain_sweep_end(c)) return 1;
 	c->h_qq = false;
 	return 0;
 }

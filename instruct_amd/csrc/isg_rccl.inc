@@ -57,8 +57,7 @@ extern "C" int isg_gather_convg(isg_ctx *c, int rank, int world, const char *id_
 		/* rank 0 publishes the id when ITS chain is done: the chains run the same number of iterations, so minutes apart at most (a chain
 		 * that was discarded for an empty cluster and re-run, InStruct.c:185-190, takes twice as long: INSTRUCT_MGPU_TIMEOUT seconds,
 		 * default half an hour).  The launcher leaves an `abort` file beside the id when a worker has failed: nobody waits for a dead rank. */
-		const char *e = getenv("INSTRUCT_MGPU_TIMEOUT");
-		const long limit_ms = 1000L * (e ? atol(e) : 1800L);
+		const long limit_ms = 1000L * env_int(getenv("INSTRUCT_MGPU_TIMEOUT"), 1800L);
 		std::string abort_path(id_path);
 		const size_t slash = abort_path.find_last_of('/');
 		abort_path = (slash == std::string::npos ? std::string("") : abort_path.substr(0, slash + 1)) + "abort";

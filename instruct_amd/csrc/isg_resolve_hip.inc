@@ -741,8 +741,7 @@ static void resolve_free(isg_ctx *c)
 /* nvalid: loci used per individual (host copy); called once per context */
 static int resolve_alloc(isg_ctx *c, const std::vector<int> &nvalid, int copies = 2, int kmax = 8)
 {
-	const char *e = getenv("INSTRUCT_ZQ_RESOLVE");
-	if (e && atoi(e) == 0) return 0;
+	if (!env_flag(getenv("INSTRUCT_ZQ_RESOLVE"), true)) return 0;
 	const int N = c->cfg.N, K = c->cfg.K;
 	if (K > kmax || (copies == 2 && c->cfg.mode == 0)) return 0; /* pre-filter rows in registers; mode 0 has no update_ZQ */
 	if (copies == 2 && ((uint64_t)c->d.Lp * (uint64_t)c->d.Amax * 32ull >= (1ull << 32) || c->d.Lp >= (1 << 24) || c->d.Amax >= (1 << 24))) return 0; /* 32-bit byte offsets into the float frequency table */
@@ -757,16 +756,14 @@ static int resolve_alloc(isg_ctx *c, const std::vector<int> &nvalid, int copies 
 	HIPCHK(hipMalloc((void **)&r->d_plan, sizeof(ResolvePlan)));
 	HIPCHK(hipMalloc((void **)&r->d_st, sizeof(ResolveState)));
 	HIPCHK(hipMalloc((void **)&r->d_gran, sizeof(unsigned long long) * (2 * ISG_RS_UMAX + 1)));
-	e = getenv("INSTRUCT_ZQ_RESOLVE_PERSIST");
-	if (e && atoi(e) == 0) r->persist = false;
+	r->persist = env_flag(getenv("INSTRUCT_ZQ_RESOLVE_PERSIST"), true);
 	/* rejected attempts per individual: about 0.46 per gamma with a spread of 0.8 sqrt(K) (measured at K = 5: 2.3, 1.8);
 	 * replaced by the previous sweep's own statistics from the second sweep on */
 	r->mu = 0.46 * K;
 	r->sigma = 0.8 * sqrt((double)K);
-	e = getenv("INSTRUCT_ZQ_RESOLVE_A");
-	if (e && atof(e) > 0.5) r->a = atof(e);
-	e = getenv("INSTRUCT_ZQ_RESOLVE_SHAPE");
-	if (e && atof(e) >= 0.0 && atof(e) <= 1.5) r->shape = atof(e);
+	const double a = env_double(getenv("INSTRUCT_ZQ_RESOLVE_A"), r->a, 0.5);
+	if (a > 0.5) r->a = a; /* (0.5 itself is not taken) */
+	r->shape = env_double(getenv("INSTRUCT_ZQ_RESOLVE_SHAPE"), r->shape, 0.0, 1.5);
 	{ /* ISG_RS_OCC units (workgroups of 4 waves) per compute unit, all resident together.  Measured at config 3 on 256 CUs, update_ZQ's
 	   * block kernel per sweep: 256 / 384 / 512 units -> 8.9 / 8.5 / 7.5 ms (a block's fixed costs -- hand-over, walk, Dirichlet --
 	   * are shared by more individuals: 33 / 44 / 54 per block); ploidy 4's block kernel holds one workgroup per compute unit */
@@ -776,8 +773,8 @@ static int resolve_alloc(isg_ctx *c, const std::vector<int> &nvalid, int copies 
 			r->units = want > ISG_RS_UMAX ? ISG_RS_UMAX : want;
 		}
 	}
-	e = getenv("INSTRUCT_ZQ_RESOLVE_UNITS");
-	if (e && atoi(e) >= 8) r->units = atoi(e) > ISG_RS_UMAX ? ISG_RS_UMAX : atoi(e);
+	const int units = (int)env_int(getenv("INSTRUCT_ZQ_RESOLVE_UNITS"), r->units, 8, INT_MAX);
+	r->units = units > ISG_RS_UMAX ? ISG_RS_UMAX : units;
 	return 0;
 }
 
@@ -808,26 +805,6 @@ static void resolve_launch_at(isg_ctx *c, isg_wh base)
 	hipLaunchKernelGGL((k_zq_at<256, KMAX>), dim3(c->cfg.N), dim3(256), 0, c->stream, c->d, base, c->alpha, (const ResolveState *)r->d_st,
 			   (const unsigned long long *)r->d_offs);
 }
-#define RS_DISPATCH(K, CALL)                   \
-	switch (K) {                           \
-	case 1: case 2: CALL(2); break;        \
-	case 3: CALL(3); break;                \
-	case 4: CALL(4); break;                \
-	case 5: CALL(5); break;                \
-	case 6: CALL(6); break;                \
-	default: CALL(8); break;               \
-	}
-/* the block kernels take K as a compile-time constant: K == KMAX (K = 1: KMAX = 2, K read at run time) */
-#define RS_DISPATCH_EXACT(K, CALL)             \
-	switch (K) {                           \
-	case 1: case 2: CALL(2); break;        \
-	case 3: CALL(3); break;                \
-	case 4: CALL(4); break;                \
-	case 5: CALL(5); break;                \
-	case 6: CALL(6); break;                \
-	case 7: CALL(7); break;                \
-	default: CALL(8); break;               \
-	}
 
 /* returns 0 and *done = true when the sweep is complete; *done = false: nothing is changed (qq restored), the caller
  * takes the chain kernels */
@@ -921,14 +898,15 @@ static int resolve_update_ZQ_with(isg_ctx *c, isg_wh base, bool *done, LB launch
 static int resolve_update_ZQ(isg_ctx *c, isg_wh base, bool *done)
 {
 	const int K = c->cfg.K;
-#define RS_BLOCK(KM) resolve_launch_block<KM>(c, base, tl, b)
-#define RS_AT(KM) resolve_launch_at<KM>(c, base)
-#define RS_PERSIST(KM) ok = resolve_launch_persist<KM>(c, base, tl)
-	return resolve_update_ZQ_with(c, base, done, [&](int b, uint64_t tl) { RS_DISPATCH_EXACT(K, RS_BLOCK) }, [&]() { RS_DISPATCH(K, RS_AT) },
-				      [&](uint64_t tl) { bool ok = false; RS_DISPATCH_EXACT(K, RS_PERSIST) return ok; });
-#undef RS_PERSIST
-#undef RS_BLOCK
-#undef RS_AT
+	/* the block kernels take K as a compile-time constant (KL_ZQ_EXACT) */
+	return resolve_update_ZQ_with(c, base, done,
+				      [&](int b, uint64_t tl) { kdispatch(KL_ZQ_EXACT(), K, [&](auto km) { resolve_launch_block<decltype(km)::value>(c, base, tl, b); }); },
+				      [&]() { kdispatch(KL_ZQ_8(), K, [&](auto km) { resolve_launch_at<decltype(km)::value>(c, base); }); },
+				      [&](uint64_t tl) {
+					      bool ok = false;
+					      kdispatch(KL_ZQ_EXACT(), K, [&](auto km) { ok = resolve_launch_persist<decltype(km)::value>(c, base, tl); });
+					      return ok;
+				      });
 }
 
 extern "C" int isg_zq_resolve_stats(isg_ctx *c, long out[8])

@@ -326,8 +326,7 @@ static void spec_free(SpecCtx *sp)
 static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid, int copies)
 {
 	*out = nullptr;
-	const char *e = getenv("INSTRUCT_ZQ_SPEC_RESOLVE");
-	if (e && atoi(e) == 0) return 0;
+	if (!env_flag(getenv("INSTRUCT_ZQ_SPEC_RESOLVE"), true)) return 0;
 	const int N = c->cfg.N, K = c->cfg.K;
 	if (K > WK_NGMAX) return 0;
 	SpecCtx *sp = new SpecCtx();
@@ -343,18 +342,12 @@ static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid
 	}
 	sp->gam0_h[N] = N * K;
 	gpos[(size_t)N * K] = B[N];
-	e = getenv("INSTRUCT_ZQ_SPEC_BAND");
-	if (e && atoi(e) >= 0 && atoi(e) <= 512) sp->band = atoi(e);
-	e = getenv("INSTRUCT_ZQ_SPEC_ROUNDS");
-	if (e && atoi(e) >= 0 && atoi(e) <= 16) sp->rounds = atoi(e);
-	e = getenv("INSTRUCT_ZQ_SPEC_KSIG");
-	if (e && atof(e) >= 1.0) sp->ksig = (float)atof(e);
-	e = getenv("INSTRUCT_ZQ_SPEC_SEG");
-	sp->walk.seg_groups = (e && atoi(e) >= 64) ? atoi(e) : 16384;
-	e = getenv("INSTRUCT_WALK_K");
-	if (e && atof(e) >= 1.0) sp->walk.kwin = atof(e);
-	e = getenv("INSTRUCT_ZQ_SPEC_TEST_ABORT");
-	sp->test_abort = e ? atoi(e) : 0;
+	sp->band = (int)env_int(getenv("INSTRUCT_ZQ_SPEC_BAND"), sp->band, 0, 512);
+	sp->rounds = (int)env_int(getenv("INSTRUCT_ZQ_SPEC_ROUNDS"), sp->rounds, 0, 16);
+	sp->ksig = (float)env_double(getenv("INSTRUCT_ZQ_SPEC_KSIG"), sp->ksig, 1.0);
+	sp->walk.seg_groups = (int)env_int(getenv("INSTRUCT_ZQ_SPEC_SEG"), 16384, 64, INT_MAX);
+	sp->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), sp->walk.kwin, 1.0);
+	sp->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_SPEC_TEST_ABORT"), 0);
 	sp->list_cap = 6 * N + 1024;
 	HIPCHK(hipMalloc((void **)&sp->d_gam0, sizeof(int) * ((size_t)N + 1)));
 	HIPCHK(hipMalloc((void **)&sp->d_gpos, sizeof(unsigned long long) * ((size_t)N * K + 1)));
@@ -362,7 +355,7 @@ static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid
 	HIPCHK(hipMalloc((void **)&sp->d_offs, sizeof(unsigned long long) * ((size_t)N + 1)));
 	HIPCHK(hipMalloc((void **)&sp->d_alo, sizeof(float) * (size_t)N * K));
 	HIPCHK(hipMalloc((void **)&sp->d_ahi, sizeof(float) * (size_t)N * K));
-	{ const char *ez = getenv("INSTRUCT_ZEXPECT_STRIP"); sp->zstrip = ez && atoi(ez) == 1; }
+	sp->zstrip = env_flag(getenv("INSTRUCT_ZEXPECT_STRIP"), false);
 	HIPCHK(hipMalloc((void **)&sp->d_list, sizeof(SpecProbe) * (size_t)sp->list_cap));
 	HIPCHK(hipMalloc((void **)&sp->d_dev, sizeof(SpecDev)));
 	HIPCHK(hipMalloc((void **)&sp->d_rs, sizeof(ResolveState)));
@@ -372,22 +365,6 @@ static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid
 	*out = sp;
 	return 0;
 }
-
-#define SPEC_DISPATCH(K, CALL)                 \
-	switch (K) {                           \
-	case 1: case 2: CALL(2); break;        \
-	case 3: CALL(3); break;                \
-	case 4: CALL(4); break;                \
-	case 5: CALL(5); break;                \
-	case 6: CALL(6); break;                \
-	case 7: case 8: CALL(8); break;        \
-	default:                               \
-		if (K <= 12) CALL(12);         \
-		else if (K <= 16) CALL(16);    \
-		else if (K <= 24) CALL(24);    \
-		else if (K <= ISG_KCAP) CALL(32); \
-		else CALL(ISG_KWIDE);          \
-	}
 
 /* launch_expect(alo, ahi) / launch_probe(grid) / launch_at(): the ploidy's kernels.  *done = false: nothing is changed (qq restored),
  * the caller takes its other paths. */
@@ -534,11 +511,8 @@ static void spec_launch_at(isg_ctx *c, SpecCtx *sp, isg_wh base)
 static int spec_update_ZQ(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done)
 {
 	const int K = c->cfg.K;
-#define SP_EXPECT(KM) spec_launch_expect<KM>(c, sp, alo, ahi)
-#define SP_PROBE(KM) spec_launch_probe<KM>(c, sp, base, grid)
-#define SP_AT(KM) spec_launch_at<KM>(c, sp, base)
-	return spec_update_ZQ_with(c, sp, base, done, [&](float *alo, float *ahi) { SPEC_DISPATCH(K, SP_EXPECT) }, [&](int grid) { SPEC_DISPATCH(K, SP_PROBE) }, [&]() { SPEC_DISPATCH(K, SP_AT) });
-#undef SP_EXPECT
-#undef SP_PROBE
-#undef SP_AT
+	return spec_update_ZQ_with(c, sp, base, done,
+				   [&](float *alo, float *ahi) { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_expect<decltype(km)::value>(c, sp, alo, ahi); }); },
+				   [&](int grid) { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_probe<decltype(km)::value>(c, sp, base, grid); }); },
+				   [&]() { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_at<decltype(km)::value>(c, sp, base); }); });
 }

@@ -384,8 +384,7 @@ static void pdev_free(PDevCtx *p)
 static int pdev_create(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const int *allelenum, int min_alleles)
 {
 	*out = nullptr;
-	const char *e = getenv("INSTRUCT_P_DEVICE");
-	if (e && atoi(e) == 0) return 0;
+	if (!env_flag(getenv("INSTRUCT_P_DEVICE"), true)) return 0;
 	PDevCtx *p = new PDevCtx();
 	std::vector<int> gidx;
 	p->gam0_h.push_back(0);
@@ -400,11 +399,8 @@ static int pdev_create(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const 
 	p->G = (int)p->gam0_h.size() - 1;
 	p->NG = (int)gidx.size();
 	if (p->G < 1) { delete p; return 0; }
-	p->walk.seg_groups = 12800; /* (config 3's 25000 groups: two segments, measured best of 4096 .. 25600; config 5 does not care) */
-	e = getenv("INSTRUCT_WALK_SEG");
-	if (e && atoi(e) >= 64) p->walk.seg_groups = atoi(e);
-	e = getenv("INSTRUCT_WALK_K");
-	if (e && atof(e) >= 1.0) p->walk.kwin = atof(e);
+	p->walk.seg_groups = (int)env_int(getenv("INSTRUCT_WALK_SEG"), 12800, 64, INT_MAX); /* (config 3's 25000 groups: two segments, measured best of 4096 .. 25600; config 5 does not care) */
+	p->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), p->walk.kwin, 1.0);
 	HIPCHK(hipMalloc((void **)&p->d_gam0, sizeof(int) * (p->G + 1)));
 	HIPCHK(hipMalloc((void **)&p->d_gidx, sizeof(int) * p->NG));
 	HIPCHK(hipMalloc((void **)&p->d_gcnt, sizeof(int) * p->NG));
