@@ -212,6 +212,10 @@ int isg_profile_reset(isg_ctx *ctx);
  * repetitions: the ceiling a streaming kernel has on this GPU, reported by bench.py beside the 8 TB/s specification */
 int isg_copy_bandwidth(int device, size_t bytes, int reps, double *gbs);
 
+/* diagnostic: device and pinned host allocations of this library alive in the process (every one is owned by a context or by a call in
+ * progress, instruct_amd/csrc/isg_devbuf.h): back at its earlier value once a context is destroyed */
+long isg_diag_live_buffers(void);
+
 /* host-only exhaustive check of the device's integer/float shortcuts (LCG step without division,
  * quotient by reciprocal + fma, table skip-ahead) against the plain formulas of random.c:19-47 */
 int isg_selftest(void);

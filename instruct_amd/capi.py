@@ -24,7 +24,7 @@ EXPORTS = [
     "isg_get_alpha", "isg_get_totallkh", "isg_get_amax", "isg_set_z", "isg_set_freq", "isg_set_qq",
     "isg_set_generation", "isg_set_self_rates", "isg_set_alpha", "isg_keyed_layout", "isg_profile_enable",
     "isg_profile_count", "isg_profile_get", "isg_profile_reset", "isg_gelman_rubin", "isg_selftest",
-    "isg_store_begin", "isg_store_step", "isg_store_fetch", "isg_zq_fallbacks", "isg_p_device_stats", "isg_zq_spec_stats", "isg_copy_bandwidth", "isg_zq_resolve_stats", "isg_zq_resolve_plan", "isg_gather_convg",
+    "isg_store_begin", "isg_store_step", "isg_store_fetch", "isg_zq_fallbacks", "isg_p_device_stats", "isg_zq_spec_stats", "isg_copy_bandwidth", "isg_diag_live_buffers", "isg_zq_resolve_stats", "isg_zq_resolve_plan", "isg_gather_convg",
     "isg_ctx_create_poly", "isg_poly_update_geno", "isg_get_poly_geno", "isg_get_poly_gs", "isg_get_poly_table", "isg_get_poly_freq2",
 ]
 
@@ -54,6 +54,8 @@ def load():
         lib.isg_run.argtypes = [C.c_void_p, C.c_long]
         lib.isg_zq_fallbacks.restype = C.c_long
         lib.isg_zq_fallbacks.argtypes = [C.c_void_p]
+        lib.isg_diag_live_buffers.restype = C.c_long
+        lib.isg_diag_live_buffers.argtypes = []
         _lib = lib
     return _lib
 
@@ -344,6 +346,11 @@ def copy_bandwidth(device=0, nbytes=1 << 30, reps=8):
     if lib.isg_copy_bandwidth(device, nbytes, reps, C.byref(g)) != 0:
         raise IsgError(lib.isg_last_error().decode())
     return g.value
+
+
+def live_buffers():
+    """device and pinned host allocations of the library alive in this process (isg_diag_live_buffers): a leak check for tests"""
+    return load().isg_diag_live_buffers()
 
 
 def gelman_rubin(vec, numchains, totrep):

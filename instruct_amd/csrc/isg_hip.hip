@@ -46,6 +46,7 @@
 #include "isg_wh.h"
 #include "isg_sampler.h"
 #include "isg_kdispatch.h"
+#include "isg_devbuf.h"
 
 #define ISG_KCAP 32  /* K of the register-resident kernel instances, and of ploidy 4 */
 #define ISG_KWIDE 64 /* diploid K above ISG_KCAP: the K-generic wide kernels (DESIGN.md §4 "K up to 64") */
@@ -138,7 +139,37 @@ struct PageAlloc {
 };
 template <class T> using hvec = std::vector<T, PageAlloc<T>>;
 
-struct isg_ctx {
+struct CoopBuf;
+/* What a context itself owns on the device, its pinned tape and its events: isg_ctx_destroy releases them in one step, after the stream
+ * has been synchronised and before the stream goes.  DevView (and PolyDev, for freqf, tab and err) are views of these. */
+struct CtxBufs {
+	DevBuf<uint8_t> d_geno, d_z;
+	DevBuf<int> d_allelenum, d_nvalid, d_cnt, d_qqnum, d_gen, d_genprop;
+	DevBuf<unsigned> d_rankwave;
+	DevBuf<double> d_freq, d_lftab, d_lltab, d_qq, d_uacc, d_indvlkh;
+	DevBuf<float> d_freqf;
+	DevBuf<int2> d_lli;
+	DevBuf<isg_wh_tables> d_tab;
+	/* device scratch */
+	DevBuf<uint64_t> d_pos;
+	DevBuf<unsigned> d_err;
+	DevBuf<double> d_S;
+	DevBuf<double> d_Fprop; /* mode 5: proposed coefficients */
+	DevBuf<double> d_tape;
+	DevBuf<CoopBuf> d_coop;
+	DevBuf<unsigned long long> d_pipe; /* k_zq_pipe's granules (one line per publishing wave) */
+	DevBuf<unsigned long long> d_spop; /* k_spop_tree: limbs of the 2^K exact sums */
+	DevBuf<double> d_qqsave;           /* qq as it was when a cooperative update_ZQ started (it is both input and output) */
+	DevBuf<int> d_state;
+	DevBuf<double> d_ratios, d_total;
+	PinnedBuf<double> htape;           /* replay update_P: the host loop's uniforms (host_tape_begin); pinned: a 2 MB copy per sweep */
+	DevEvent ev_tape;                  /* ... the tape has arrived (update_P_ahead) */
+	DevEvent ev_cnt;                   /* replay update_P: the counts have arrived (the tape is still on its way) */
+	/* CHAIN running means kept on the device (isg_store_*): qq, qq2 [N][K]; indvlkh, gen, gen2 [N]; freq, freq2 in the
+	 * device order of d.freq */
+	DevBuf<double> st_qq, st_qq2, st_lkh, st_gen, st_gen2, st_freq, st_freq2;
+};
+struct isg_ctx : CtxBufs {
 	isg_config cfg;
 	ResolveCtx *rs = nullptr; /* replay update_ZQ: start positions resolved block-wise (isg_resolve_hip.inc) */
 	SpecCtx *zspec = nullptr; /* replay update_ZQ: start positions resolved from intervals of shapes (isg_spec_hip.inc) */
@@ -169,50 +200,30 @@ struct isg_ctx {
 	uint64_t iter;
 	uint64_t ky[9];
 	isg_wh_tables tab_h;
-	/* device scratch */
-	uint64_t *d_pos;
-	unsigned *d_err;
-	double *d_S;
-	double *d_Fprop; /* mode 5: proposed coefficients */
-	double *d_tape;
-	uint64_t tape_cap, nvalid_total;
-	void *d_coop;
+	uint64_t nvalid_total;
 	int coop; /* 1: several workgroups per individual in the replay-schedule ZQ kernel */
 	int spec; /* 1: ... with the next individual's Z drawn ahead for the likely start positions (INSTRUCT_ZQ_SPEC=0 disables) */
 	int xcd;  /* 1: try to place the cooperating workgroups on one XCD (INSTRUCT_ZQ_XCD=1 enables) */
 	int pipe; /* 1: draw waves + one control wave per workgroup (k_zq_pipe; INSTRUCT_ZQ_PIPE=0 disables) */
 	int pipe_xcd; /* 1: its workgroups on one XCD when they fit (INSTRUCT_ZQ_PIPE_XCD=0 disables) */
-	unsigned long long *d_pipe = nullptr; /* its granules (one line per publishing wave) */
-	unsigned long long *d_spop = nullptr; /* k_spop_tree: limbs of the 2^K exact sums */
 	bool counted = false;                 /* in g_live_ctx */
 	double host_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* INSTRUCT_HOST_TIMING=1: seconds in the stages of replay update_P's host side */
 	long host_n = 0;
 	bool host_timing = false;
 	std::vector<void *> pinned;           /* host vectors registered with the runtime (pin_host): the per-sweep copies of update_P */
-	hipEvent_t ev_tape = nullptr;         /* ... the tape has arrived (update_P_ahead) */
 	bool ahead_valid = false;             /* counts and tape of the NEXT update_P were requested at the end of update_alpha ... */
 	isg_wh ahead_rng;                     /* ... for this stream position (Z unchanged since: every writer of Z clears the flag) */
 	uint64_t ahead_ngamma = 0;
-	hipEvent_t ev_cnt = nullptr;          /* replay update_P: the counts have arrived (the tape is still on its way) */
-	double *htape = nullptr;              /* replay update_P: the host loop's uniforms (host_tape_begin); pinned: a 2 MB copy per sweep */
-	uint64_t htape_cap = 0;
 	std::vector<double> pshape;           /* ... the shapes of its gammas in stream order ... */
 	std::vector<std::array<double, 5>> pcoef; /* ... and rgamma2's shape-only constants (HostGammaCoef) */
 	uint64_t htape_len = 0;
 	int host_tape = 1;                    /* INSTRUCT_HOST_TAPE=0: the host loop steps the generator itself */
 	int spop_tree = 1;                    /* INSTRUCT_SPOP_TREE=0: the one-workgroup k_spop always */
-	size_t pipe_cap = 0;
-	double *d_qqsave = nullptr;           /* qq as it was when a cooperative update_ZQ started (it is both input and output) */
 	int test_abort = 0;                   /* INSTRUCT_ZQ_TEST_ABORT=n: the n-th cooperative sweep is treated as aborted (tests) */
 	long zq_fallbacks = 0;                /* sweeps redone by the single-workgroup kernel */
-	int *d_state;
-	double *d_ratios, *d_total;
 	hvec<double> ratios_h;
 	/* which host mirrors are current */
 	bool h_qq, h_gen, h_S, h_lkh;
-	/* CHAIN running means kept on the device (isg_store_*): qq, qq2 [N][K]; indvlkh, gen, gen2 [N]; freq, freq2 in the
-	 * device order of d.freq */
-	double *st_qq = nullptr, *st_qq2 = nullptr, *st_lkh = nullptr, *st_gen = nullptr, *st_gen2 = nullptr, *st_freq = nullptr, *st_freq2 = nullptr;
 	long st_step = 0;
 	bool st_on = false;
 	/* profiling */
@@ -3244,20 +3255,8 @@ static int host_tape_begin(isg_ctx *c, uint64_t ngamma, isg_cursor *cur)
 	c->htape_len = 0;
 	if (!c->host_tape || ngamma < 4096) return 0;
 	const uint64_t need = 3 * ngamma + 65536;
-	if (need > c->tape_cap) {
-		if (c->d_tape) HIPCHK(hipFree(c->d_tape));
-		c->d_tape = nullptr;
-		c->tape_cap = 0;
-		HIPCHK(hipMalloc((void **)&c->d_tape, sizeof(double) * need));
-		c->tape_cap = need;
-	}
-	if (c->htape_cap < need) {
-		if (c->htape) (void)hipHostFree(c->htape);
-		c->htape = nullptr;
-		c->htape_cap = 0;
-		HIPCHK(hipHostMalloc((void **)&c->htape, sizeof(double) * need, hipHostMallocDefault));
-		c->htape_cap = need;
-	}
+	HIPCHK(c->d_tape.grow(need));
+	HIPCHK(c->htape.grow(need));
 	prof_begin(c);
 	hipLaunchKernelGGL(k_tape, dim3((unsigned)((need + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, c->rng, (unsigned long long)need, c->d_tape);
 	prof_end(c, "k_tape_host");
@@ -3278,7 +3277,7 @@ static void pin_host(isg_ctx *c, void *ptr, size_t bytes)
 #define HOST_T(c, k, t0) do { if ((c)->host_timing) { const auto t1_ = std::chrono::steady_clock::now(); (c)->host_t[k] += std::chrono::duration<double>(t1_ - (t0)).count(); (t0) = t1_; } } while (0)
 static int counts_mark(isg_ctx *c)
 {
-	if (!c->ev_cnt) HIPCHK(hipEventCreateWithFlags(&c->ev_cnt, hipEventDisableTiming));
+	if (!c->ev_cnt) HIPCHK(hipEventCreateWithFlags(&c->ev_cnt.e, hipEventDisableTiming));
 	HIPCHK(hipEventRecord(c->ev_cnt, c->stream));
 	return 0;
 }
@@ -3304,6 +3303,7 @@ static void host_tape_end(isg_ctx *c, isg_cursor *cur)
 }
 
 extern "C" const char *isg_last_error(void) { return g_err.c_str(); }
+extern "C" long isg_diag_live_buffers(void) { return g_live_buffers.load(); }
 
 /* The cooperative replay kernels hand data between workgroups by polling, so every workgroup of the launch must be
  * resident at the same time: `blocks` of `threads` threads have to fit on the device's CUs at this kernel's occupancy. */
@@ -3332,7 +3332,6 @@ static void ctx_count(isg_ctx *c, int delta)
 
 /* ploidy 4 (isg_poly_hip.inc, included further down) */
 static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, const int32_t *seq, isg_ctx **out);
-static void poly_ctx_destroy(isg_ctx *c);
 static int poly_update_P(isg_ctx *c);
 static int poly_update_S_POP(isg_ctx *c);
 static int poly_update_ZQ(isg_ctx *c, int init_flag);
@@ -3347,9 +3346,43 @@ static int indiv_cal_lkh_F(isg_ctx *c);
 static int inbreed_update_F_POP(isg_ctx *c);
 static int inbreed_cal_lkh(isg_ctx *c);
 static int inbreed_alloc(isg_ctx *c);
-static void inbreed_free(isg_ctx *c);
-static void store_free(isg_ctx *c);
 #define NOT_POLY(c, what) if ((c)->poly) return fail(what ": not part of the ploidy 4 chain (poly_geno.c:98-116)")
+
+/* What the diploid and the ploidy 4 contexts set up alike: the host mirrors (nS values of S), the vectors the per-sweep copies of update_P go
+ * through, the stream's origin, the Wichmann-Hill tables and the position and error words.  c->Amax is set. */
+static int ctx_init_common(isg_ctx *c, const std::vector<int> &nvalid, int Lp, int KP, size_t nS)
+{
+	const int N = c->cfg.N, L = c->cfg.L, K = c->cfg.K, Amax = c->Amax;
+	c->freq.assign((size_t)K * L * Amax, 0.0);
+	c->freq_stage.assign((size_t)Lp * Amax * KP, 0.0);
+	c->qq.assign((size_t)N * K, 0.0);
+	c->qqnum.assign((size_t)N * K, 0);
+	c->gen.assign(N, 0);
+	c->S.assign(nS, 0.0);
+	c->state.assign(K, 0);
+	c->indvlkh.assign(N, 0.0);
+	c->cnt_h.assign((size_t)L * Amax * K, 0);
+	pin_host(c, c->cnt_h.data(), sizeof(int) * c->cnt_h.size());
+	pin_host(c, c->freq_stage.data(), sizeof(double) * c->freq_stage.size());
+	c->nvalid_total = 0;
+	for (int i = 0; i < N; i++) c->nvalid_total += (uint64_t)nvalid[i];
+	c->alpha = 0;
+	c->totallkh = 0;
+	c->iter = 0;
+	c->rng.s1 = 13; c->rng.s2 = 4; c->rng.s3 = 1972; /* random.c:10-12 */
+	c->origin = c->rng;
+	c->raw_seed[0] = 13; c->raw_seed[1] = 4; c->raw_seed[2] = 1972;
+	c->raw_valid = true;
+	c->prof = false;
+	c->h_qq = c->h_gen = c->h_S = c->h_lkh = true;
+	isg_wh_tables_init(&c->tab_h);
+	HIPCHK(c->d_tab.upload(&c->tab_h, 1));
+	HIPCHK(c->d_pos.alloc_zero(4));
+	HIPCHK(c->d_err.alloc_zero(4));
+	c->d.tab = c->d_tab;
+	c->d.err = c->d_err;
+	return 0;
+}
 
 /* a context under construction: destroyed (device allocations, stream and all) unless construction reaches its end */
 struct CtxGuard {
@@ -3400,50 +3433,37 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	memset(&d, 0, sizeof(d));
 	d.N = N; d.L = L; d.Lp = Lp; d.K = K; d.KP = KP; d.Amax = Amax; d.mode = cfg->mode; d.type_freq = cfg->type_freq;
 	HIPCHK(hipStreamCreate(&c->stream));
-	void *p;
-#define DALLOC(field, type, count)                                  \
-	HIPCHK(hipMalloc(&p, sizeof(type) * (size_t)(count)));      \
-	HIPCHK(hipMemset(p, 0, sizeof(type) * (size_t)(count)));    \
-	field = (type *)p;
-	uint8_t *dg;
-	DALLOC(dg, uint8_t, (size_t)N * Lp * 2);
-	d.geno = dg;
-	HIPCHK(hipMemcpy(dg, pk.data(), pk.size(), hipMemcpyHostToDevice));
-	DALLOC(d.z, uint8_t, (size_t)N * Lp * 2);
+	HIPCHK(c->d_geno.upload(pk));
+	d.geno = c->d_geno;
+	HIPCHK(c->d_z.alloc_zero((size_t)N * Lp * 2));
+	d.z = c->d_z;
 	HIPCHK(hipMemset(d.z, 0xff, (size_t)N * Lp * 2));
-	int *dan, *dnv;
-	DALLOC(dan, int, L);
-	HIPCHK(hipMemcpy(dan, allelenum, sizeof(int) * L, hipMemcpyHostToDevice));
-	d.allelenum = dan;
-	DALLOC(dnv, int, N);
-	HIPCHK(hipMemcpy(dnv, nvalid.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-	d.nvalid = dnv;
-	DALLOC(d.freq, double, (size_t)Lp * Amax * KP);
+	HIPCHK(c->d_allelenum.upload(allelenum, L));
+	d.allelenum = c->d_allelenum;
+	HIPCHK(c->d_nvalid.upload(nvalid));
+	d.nvalid = c->d_nvalid;
+	HIPCHK(c->d_freq.alloc_zero((size_t)Lp * Amax * KP));
+	d.freq = c->d_freq;
 	d.KPF = (K + 3) & ~3;
-	DALLOC(d.freqf, float, (size_t)Lp * Amax * d.KPF);
-	d.lftab = d.lltab = nullptr;
-	d.lli = nullptr;
-	d.lli_F = 0;
+	HIPCHK(c->d_freqf.alloc_zero((size_t)Lp * Amax * d.KPF));
+	d.freqf = c->d_freqf;
 	if (cfg->type_freq == 1 || cfg->mode == 0) { /* (-y 0 mixes the frequencies with the individual's qq: no tables) */
 		if (env_flag(getenv("INSTRUCT_LL_TABLES"), true)) {
-			DALLOC(d.lftab, double, (size_t)L * Amax * K);
+			HIPCHK(c->d_lftab.alloc_zero((size_t)L * Amax * K));
 			const size_t ent = (size_t)50 * L * Amax * Amax * K;
 			const size_t enti = 1 + (size_t)50 * Lp * Amax * Amax * K + (size_t)Lp * Amax * K; /* the integer form, locus innermost (k_loglik_int) */
 			if (cfg->mode == 2 && env_flag(getenv("INSTRUCT_LL_INT"), true) && enti * sizeof(int2) <= ((size_t)1 << 30)) {
-				DALLOC(d.lli, int2, enti);
+				HIPCHK(c->d_lli.alloc_zero(enti));
 				d.lli_F = (unsigned)(1 + (size_t)50 * Lp * Amax * Amax * K);
-			} else if (cfg->mode == 2 && ent * sizeof(double) <= ((size_t)1 << 30)) { DALLOC(d.lltab, double, ent); } /* (mode 3: unclamped initial generations) */
+			} else if (cfg->mode == 2 && ent * sizeof(double) <= ((size_t)1 << 30)) { HIPCHK(c->d_lltab.alloc_zero(ent)); } /* (mode 3: unclamped initial generations) */
 			if (cfg->mode == 4) { /* one slot: log genofreq_inbreedcoff.  Mode 4 has no table-free path: up to half of what the device has free */
 				size_t fr = 0, tot = 0;
 				if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = (size_t)1 << 31;
-				if ((ent / 50) * sizeof(double) <= fr / 2) { DALLOC(d.lltab, double, ent / 50); }
+				if ((ent / 50) * sizeof(double) <= fr / 2) { HIPCHK(c->d_lltab.alloc_zero(ent / 50)); }
 			}
+			d.lftab = c->d_lftab; d.lltab = c->d_lltab; d.lli = c->d_lli;
 		}
 	}
-	c->d_tape = nullptr;
-	c->tape_cap = 0;
-	c->nvalid_total = 0;
-	for (int i = 0; i < N; i++) c->nvalid_total += (uint64_t)nvalid[i];
 	if (resolve_alloc(c, nvalid)) return 1;
 	if (cfg->rng_sched == ISG_SCHED_REPLAY && pdev_create(c, &c->pdev, L, K, Amax, allelenum, 1)) return 1;
 	if (cfg->rng_sched == ISG_SCHED_REPLAY && cfg->mode != 0 && spec_create(c, &c->zspec, nvalid, 2)) return 1;
@@ -3457,16 +3477,12 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 				for (int j = 64 * w; j < 64 * (w + 1) && j < Lp; j++) run += (pk[((size_t)i * Lp + j) * 2] != 0xff) ? 1u : 0u;
 			}
 		}
-		unsigned *drw;
-		DALLOC(drw, unsigned, (size_t)N * nwv);
-		HIPCHK(hipMemcpy(drw, rw.data(), sizeof(unsigned) * rw.size(), hipMemcpyHostToDevice));
-		d.rankwave = drw;
+		HIPCHK(c->d_rankwave.upload(rw));
+		d.rankwave = c->d_rankwave;
 		d.nwv = nwv;
 	}
 	{
-		CoopBuf *cbp;
-		DALLOC(cbp, CoopBuf, 1);
-		c->d_coop = cbp;
+		HIPCHK(c->d_coop.alloc_zero(1));
 		c->coop = env_flag(getenv("INSTRUCT_ZQ_COOP"), true);
 		c->spec = env_flag(getenv("INSTRUCT_ZQ_SPEC"), true);
 		c->xcd = env_flag(getenv("INSTRUCT_ZQ_XCD"), false); /* experimental, off by default: measured gain at config 3 is within noise */
@@ -3476,50 +3492,23 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 		c->pipe_xcd = env_flag(getenv("INSTRUCT_ZQ_PIPE_XCD"), true);
 		c->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_TEST_ABORT"), 0);
 	}
-	DALLOC(d.cnt, int, (size_t)Lp * Amax * K);
-	DALLOC(d.qq, double, (size_t)N * K);
-	DALLOC(c->d_qqsave, double, (size_t)N * K);
-	DALLOC(d.qqnum, int, (size_t)N * K);
-	DALLOC(d.gen, int, N);
-	DALLOC(d.genprop, int, N);
-	DALLOC(d.uacc, double, N);
-	DALLOC(d.indvlkh, double, N);
-	isg_wh_tables_init(&c->tab_h);
-	isg_wh_tables *dt;
-	DALLOC(dt, isg_wh_tables, 1);
-	HIPCHK(hipMemcpy(dt, &c->tab_h, sizeof(isg_wh_tables), hipMemcpyHostToDevice));
-	d.tab = dt;
-	DALLOC(c->d_pos, uint64_t, 4);
-	DALLOC(c->d_err, unsigned, 4);
-	DALLOC(c->d_S, double, ((cfg->mode == 3 || cfg->mode == 5) && N > ISG_KWIDE) ? N : ISG_KWIDE); /* modes 3, 5: one value per individual */
-	c->d_Fprop = nullptr;
-	if (cfg->mode == 5) { DALLOC(c->d_Fprop, double, N); }
-	DALLOC(c->d_state, int, ISG_KWIDE);
-	DALLOC(c->d_ratios, double, (size_t)N * K);
-	DALLOC(c->d_total, double, 1);
+	HIPCHK(c->d_cnt.alloc_zero((size_t)Lp * Amax * K));
+	HIPCHK(c->d_qq.alloc_zero((size_t)N * K));
+	HIPCHK(c->d_qqsave.alloc_zero((size_t)N * K));
+	HIPCHK(c->d_qqnum.alloc_zero((size_t)N * K));
+	HIPCHK(c->d_gen.alloc_zero(N));
+	HIPCHK(c->d_genprop.alloc_zero(N));
+	HIPCHK(c->d_uacc.alloc_zero(N));
+	HIPCHK(c->d_indvlkh.alloc_zero(N));
+	d.cnt = c->d_cnt; d.qq = c->d_qq; d.qqnum = c->d_qqnum; d.gen = c->d_gen; d.genprop = c->d_genprop; d.uacc = c->d_uacc; d.indvlkh = c->d_indvlkh;
+	const bool per_indiv = cfg->mode == 3 || cfg->mode == 5; /* modes 3, 5: one value of S per individual */
+	if (ctx_init_common(c, nvalid, Lp, KP, per_indiv ? N : K)) return 1;
+	HIPCHK(c->d_S.alloc_zero(per_indiv && N > ISG_KWIDE ? N : ISG_KWIDE));
+	if (cfg->mode == 5) HIPCHK(c->d_Fprop.alloc_zero(N));
+	HIPCHK(c->d_state.alloc_zero(ISG_KWIDE));
+	HIPCHK(c->d_ratios.alloc_zero((size_t)N * K));
+	HIPCHK(c->d_total.alloc_zero(1));
 	c->ratios_h.assign((size_t)N * K, 0.0);
-	c->h_qq = c->h_gen = c->h_S = c->h_lkh = true;
-	d.err = c->d_err;
-#undef DALLOC
-	c->freq.assign((size_t)K * L * Amax, 0.0);
-	c->freq_stage.assign((size_t)Lp * Amax * KP, 0.0);
-	c->qq.assign((size_t)N * K, 0.0);
-	c->qqnum.assign((size_t)N * K, 0);
-	c->gen.assign(N, 0);
-	c->S.assign((cfg->mode == 3 || cfg->mode == 5) ? N : K, 0.0); /* modes 3, 5: one value per individual */
-	c->state.assign(K, 0);
-	c->indvlkh.assign(N, 0.0);
-	c->cnt_h.assign((size_t)L * Amax * K, 0);
-	pin_host(c, c->cnt_h.data(), sizeof(int) * c->cnt_h.size());
-	pin_host(c, c->freq_stage.data(), sizeof(double) * c->freq_stage.size());
-	c->alpha = 0;
-	c->totallkh = 0;
-	c->iter = 0;
-	c->rng.s1 = 13; c->rng.s2 = 4; c->rng.s3 = 1972; /* random.c:10-12 */
-	c->origin = c->rng;
-	c->raw_seed[0] = 13; c->raw_seed[1] = 4; c->raw_seed[2] = 1972;
-	c->raw_valid = true;
-	c->prof = false;
 	keyed_layout(c);
 	if (cfg->mode == 0 && !d.lftab) return fail("isg_ctx_create: mode 0 needs its log frequency table (INSTRUCT_LL_TABLES must not be 0)");
 	if (cfg->mode == 4) {
@@ -3529,48 +3518,6 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	guard.release();
 	*out = c;
 	return 0;
-}
-
-extern "C" void isg_ctx_destroy(isg_ctx *c)
-{
-	if (!c) return;
-	ctx_count(c, -1);
-	if (c->host_timing && c->host_n > 0)
-		fprintf(stderr, "replay update_P host side, ms per sweep over %ld sweeps: counts %.3f  shapes %.3f  constants %.3f  tape %.3f  draws %.3f  upload %.3f\n", c->host_n,
-			1e3 * c->host_t[0] / c->host_n, 1e3 * c->host_t[1] / c->host_n, 1e3 * c->host_t[2] / c->host_n, 1e3 * c->host_t[3] / c->host_n, 1e3 * c->host_t[4] / c->host_n, 1e3 * c->host_t[5] / c->host_n);
-	(void)hipSetDevice(c->cfg.device);
-	(void)hipStreamSynchronize(c->stream);
-	if (c->htape) (void)hipHostFree(c->htape);
-	c->htape = nullptr;
-	if (c->ev_cnt) (void)hipEventDestroy(c->ev_cnt);
-	c->ev_cnt = nullptr;
-	if (c->ev_tape) (void)hipEventDestroy(c->ev_tape);
-	c->ev_tape = nullptr;
-	for (void *q : c->pinned) (void)hipHostUnregister(q);
-	c->pinned.clear();
-	store_free(c);
-	resolve_free(c);
-	pdev_free(c->pdev);
-	c->pdev = nullptr;
-	spec_free(c->zspec);
-	c->zspec = nullptr;
-	if (c->poly) {
-		poly_ctx_destroy(c);
-		prof_collect(c);
-		for (auto e : c->prof_free) (void)hipEventDestroy(e);
-		(void)hipStreamDestroy(c->stream);
-		delete c;
-		return;
-	}
-	inbreed_free(c);
-	DevView &d = c->d;
-	(void)hipFree((void *)d.geno); (void)hipFree(d.z); (void)hipFree((void *)d.allelenum); (void)hipFree((void *)d.nvalid); (void)hipFree(d.freq); (void)hipFree(d.freqf); (void)hipFree(d.lftab); (void)hipFree(d.lltab); (void)hipFree(d.lli); (void)hipFree(c->d_tape); (void)hipFree((void *)d.rankwave); (void)hipFree(c->d_coop); (void)hipFree(c->d_pipe); (void)hipFree(c->d_spop); (void)hipFree(d.cnt);
-	(void)hipFree(d.qq); (void)hipFree(c->d_qqsave); (void)hipFree(d.qqnum); (void)hipFree(d.gen); (void)hipFree(d.genprop); (void)hipFree(d.uacc); (void)hipFree(d.indvlkh);
-	(void)hipFree((void *)d.tab); (void)hipFree(c->d_pos); (void)hipFree(c->d_err); (void)hipFree(c->d_S); (void)hipFree(c->d_Fprop); (void)hipFree(c->d_state); (void)hipFree(c->d_ratios); (void)hipFree(c->d_total);
-	prof_collect(c);
-	for (auto e : c->prof_free) (void)hipEventDestroy(e);
-	(void)hipStreamDestroy(c->stream);
-	delete c;
 }
 
 extern "C" int isg_set_seeds(isg_ctx *c, long s1, long s2, long s3)
@@ -3744,7 +3691,7 @@ static int update_P_ahead(isg_ctx *c)
 	for (int j = 0; j < L; j++) ngamma += (c->allelenum[j] > 1) ? (uint64_t)c->allelenum[j] * K : 0;
 	isg_cursor cur;
 	if (host_tape_begin(c, ngamma, &cur)) return 1;
-	if (!c->ev_tape) HIPCHK(hipEventCreateWithFlags(&c->ev_tape, hipEventDisableTiming));
+	if (!c->ev_tape) HIPCHK(hipEventCreateWithFlags(&c->ev_tape.e, hipEventDisableTiming));
 	HIPCHK(hipEventRecord(c->ev_tape, c->stream));
 	c->ahead_rng = c->rng;
 	c->ahead_ngamma = ngamma;
@@ -3847,7 +3794,7 @@ extern "C" int isg_update_S_POP(isg_ctx *c)
 	isg_wh start = is_keyed(c) ? isg_wh_jump(&c->tab_h, c->origin, iter_base(c) + c->ky[KY_OFFS]) : c->rng;
 	if (c->cfg.back_refl == 1 && K <= ISG_SPOP_TREE_K && c->spop_tree) {
 		const size_t nb = sizeof(unsigned long long) * 5 * ((size_t)1 << K);
-		if (!c->d_spop) HIPCHK(hipMalloc((void **)&c->d_spop, sizeof(unsigned long long) * 5 * ((size_t)1 << ISG_SPOP_TREE_K)));
+		if (!c->d_spop) HIPCHK(c->d_spop.alloc(5 * ((size_t)1 << ISG_SPOP_TREE_K)));
 		HIPCHK(hipMemsetAsync(c->d_spop, 0, nb, c->stream));
 		prof_begin(c);
 		hipLaunchKernelGGL(k_spop_tree, dim3((c->cfg.N + 255) / 256, 1u << K), dim3(256), 0, c->stream, c->d, (const double *)c->d_S, start, c->d_spop);
@@ -3920,13 +3867,7 @@ static bool coop_sweep_failed(isg_ctx *c, const unsigned flags[2])
  * device view points at them. */
 static int tape_fill(isg_ctx *c, isg_wh base, uint64_t need)
 {
-	if (need > c->tape_cap) {
-		if (c->d_tape) HIPCHK(hipFree(c->d_tape));
-		c->d_tape = nullptr;
-		c->tape_cap = 0;
-		HIPCHK(hipMalloc((void **)&c->d_tape, sizeof(double) * need));
-		c->tape_cap = need;
-	}
+	HIPCHK(c->d_tape.grow(need));
 	if (need) {
 		prof_begin(c);
 		hipLaunchKernelGGL(k_tape, dim3((unsigned)((need + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, base, (unsigned long long)need, c->d_tape);
@@ -4019,13 +3960,7 @@ extern "C" int isg_update_ZQ(isg_ctx *c, int init_flag)
 		const int ppack = (GP <= 32 && c->pipe_xcd) ? 1 : 0;
 		if (pipe) {
 			const size_t need_words = (size_t)ISG_COOP_RING * GP * ISG_PIPE_DW * ISG_PIPE_STRIDE;
-			if (need_words > c->pipe_cap) {
-				if (c->d_pipe) HIPCHK(hipFree(c->d_pipe));
-				c->d_pipe = nullptr;
-				c->pipe_cap = 0;
-				HIPCHK(hipMalloc((void **)&c->d_pipe, need_words * sizeof(unsigned long long)));
-				c->pipe_cap = need_words;
-			}
+			HIPCHK(c->d_pipe.grow(need_words));
 			HIPCHK(hipMemsetAsync(c->d_pipe, 0, need_words * sizeof(unsigned long long), c->stream));
 		}
 		HIPCHK(hipMemcpyAsync(c->d_qqsave, c->d.qq, sizeof(double) * (size_t)c->cfg.N * K, hipMemcpyDeviceToDevice, c->stream));
@@ -4122,6 +4057,30 @@ extern "C" int isg_cal_lkh(isg_ctx *c)
 
 #include "isg_poly_hip.inc"
 #include "isg_modes_hip.inc"
+
+/* after the stream has drained: the pinned vectors, the sub-contexts and every buffer, then the profiling events, the stream last */
+extern "C" void isg_ctx_destroy(isg_ctx *c)
+{
+	if (!c) return;
+	ctx_count(c, -1);
+	if (c->host_timing && c->host_n > 0)
+		fprintf(stderr, "replay update_P host side, ms per sweep over %ld sweeps: counts %.3f  shapes %.3f  constants %.3f  tape %.3f  draws %.3f  upload %.3f\n", c->host_n,
+			1e3 * c->host_t[0] / c->host_n, 1e3 * c->host_t[1] / c->host_n, 1e3 * c->host_t[2] / c->host_n, 1e3 * c->host_t[3] / c->host_n, 1e3 * c->host_t[4] / c->host_n, 1e3 * c->host_t[5] / c->host_n);
+	(void)hipSetDevice(c->cfg.device);
+	(void)hipStreamSynchronize(c->stream);
+	for (void *q : c->pinned) (void)hipHostUnregister(q);
+	c->pinned.clear();
+	delete c->rs;
+	delete c->pdev;
+	delete c->zspec;
+	delete c->poly;
+	delete c->inb;
+	static_cast<CtxBufs &>(*c) = CtxBufs(); /* every buffer and event of the context itself */
+	prof_collect(c);
+	for (auto e : c->prof_free) (void)hipEventDestroy(e);
+	(void)hipStreamDestroy(c->stream);
+	delete c;
+}
 
 extern "C" int isg_update_Z(isg_ctx *c, int init_flag) /* mode 0: update_Z, mcmc.c:1094-1120 (zz[i] is returned by isg_get_generation) */
 {
@@ -4483,16 +4442,14 @@ __global__ void k_store_chn(const double *qq, double *mqq, double *mqq2, size_t 
 }
 static void store_free(isg_ctx *c)
 {
-	(void)hipFree(c->st_qq); (void)hipFree(c->st_qq2); (void)hipFree(c->st_lkh); (void)hipFree(c->st_gen); (void)hipFree(c->st_gen2);
-	(void)hipFree(c->st_freq); (void)hipFree(c->st_freq2);
-	c->st_qq = c->st_qq2 = c->st_lkh = c->st_gen = c->st_gen2 = c->st_freq = c->st_freq2 = nullptr;
+	for (DevBuf<double> *b : {&c->st_qq, &c->st_qq2, &c->st_lkh, &c->st_gen, &c->st_gen2, &c->st_freq, &c->st_freq2}) b->reset();
 	c->st_on = false;
 	c->st_step = 0;
 }
-static int store_alloc_ones(isg_ctx *c, double **p, size_t n)
+static int store_alloc_ones(isg_ctx *c, DevBuf<double> *p, size_t n)
 {
-	HIPCHK(hipMalloc((void **)p, sizeof(double) * n));
-	hipLaunchKernelGGL(k_store_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, *p, n, 1.0);
+	HIPCHK(p->alloc(n));
+	hipLaunchKernelGGL(k_store_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, p->get(), n, 1.0);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -4619,9 +4576,9 @@ extern "C" int isg_copy_bandwidth(int device, size_t bytes, int reps, double *gb
 	*gbs = 0;
 	HIPCHK(hipSetDevice(device));
 	const size_t n = bytes / 16;
-	uint4 *a = nullptr, *b = nullptr;
-	HIPCHK(hipMalloc((void **)&a, n * 16));
-	if (hipMalloc((void **)&b, n * 16) != hipSuccess) { (void)hipFree(a); return fail("isg_copy_bandwidth: out of device memory"); }
+	DevBuf<uint4> a, b;
+	HIPCHK(a.alloc(n));
+	if (b.alloc(n) != hipSuccess) return fail("isg_copy_bandwidth: out of device memory");
 	HIPCHK(hipMemset(a, 1, n * 16));
 	hipEvent_t e0, e1;
 	HIPCHK(hipEventCreate(&e0));
@@ -4629,16 +4586,15 @@ extern "C" int isg_copy_bandwidth(int device, size_t bytes, int reps, double *gb
 	int cus = 256;
 	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
 	const dim3 grid((unsigned)(cus * 8));
-	for (int w = 0; w < 2; w++) hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, 0, (const uint4 *)a, b, n);
+	for (int w = 0; w < 2; w++) hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, 0, (const uint4 *)a, b.get(), n);
 	HIPCHK(hipEventRecord(e0, 0));
-	for (int r = 0; r < reps; r++) hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, 0, (const uint4 *)a, b, n);
+	for (int r = 0; r < reps; r++) hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, 0, (const uint4 *)a, b.get(), n);
 	HIPCHK(hipEventRecord(e1, 0));
 	HIPCHK(hipEventSynchronize(e1));
 	float ms = 0;
 	HIPCHK(hipEventElapsedTime(&ms, e0, e1));
 	*gbs = 2.0 * (double)(n * 16) * reps / (ms * 1e-3) / 1e9; /* read + written */
 	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-	(void)hipFree(a); (void)hipFree(b);
 	return 0;
 }
 

@@ -18,11 +18,11 @@
  * 2 K cluster sums come from one launch and the Metropolis steps are decided in order on the host.
  */
 struct InbreedCtx {
-	int *d_npair;   /* [L][Amax][Amax][K] loci with both copies in cluster k, by allele pair (a0, a1) as stored */
-	int *d_cntmix;  /* [L][Amax][K] allele copies of the other loci */
-	unsigned long long *d_nhet; /* [1] heterozygous loci among those */
-	unsigned long long *d_acc;  /* exact accumulators: slot 0 fixed terms, 1 + k current, 1 + K + k proposed */
-	double *d_F;    /* [2][KCAP] current and proposed coefficients */
+	DevBuf<int> d_npair;   /* [L][Amax][Amax][K] loci with both copies in cluster k, by allele pair (a0, a1) as stored */
+	DevBuf<int> d_cntmix;  /* [L][Amax][K] allele copies of the other loci */
+	DevBuf<unsigned long long> d_nhet; /* [1] heterozygous loci among those */
+	DevBuf<unsigned long long> d_acc;  /* exact accumulators: slot 0 fixed terms, 1 + k current, 1 + K + k proposed */
+	DevBuf<double> d_F;    /* [2][KCAP] current and proposed coefficients */
 };
 
 /* genofreq_inbreedcoff (mcmc.c:1705-1723) */
@@ -133,26 +133,12 @@ static int inbreed_alloc(isg_ctx *c)
 	const int L = c->cfg.L, K = c->cfg.K, A = c->Amax;
 	InbreedCtx *ib = new InbreedCtx();
 	c->inb = ib;
-	void *vp;
-#define IALLOC(field, type, count)                              \
-	HIPCHK(hipMalloc(&vp, sizeof(type) * (size_t)(count)));  \
-	HIPCHK(hipMemset(vp, 0, sizeof(type) * (size_t)(count))); \
-	field = (type *)vp;
-	IALLOC(ib->d_npair, int, (size_t)L * A * A * K);
-	IALLOC(ib->d_cntmix, int, (size_t)L * A * K);
-	IALLOC(ib->d_nhet, unsigned long long, 1);
-	IALLOC(ib->d_acc, unsigned long long, 5 * (2 * ISG_KWIDE + 2));
-	IALLOC(ib->d_F, double, 2 * ISG_KWIDE);
-#undef IALLOC
+	HIPCHK(ib->d_npair.alloc_zero((size_t)L * A * A * K));
+	HIPCHK(ib->d_cntmix.alloc_zero((size_t)L * A * K));
+	HIPCHK(ib->d_nhet.alloc_zero(1));
+	HIPCHK(ib->d_acc.alloc_zero(5 * (2 * ISG_KWIDE + 2)));
+	HIPCHK(ib->d_F.alloc_zero(2 * ISG_KWIDE));
 	return 0;
-}
-static void inbreed_free(isg_ctx *c)
-{
-	InbreedCtx *ib = c->inb;
-	if (!ib) return;
-	(void)hipFree(ib->d_npair); (void)hipFree(ib->d_cntmix); (void)hipFree(ib->d_nhet); (void)hipFree(ib->d_acc); (void)hipFree(ib->d_F);
-	delete ib;
-	c->inb = nullptr;
 }
 
 static int inbreed_update_F_POP(isg_ctx *c) /* update_inbreedcoff_POP, mcmc.c:986-1051 */

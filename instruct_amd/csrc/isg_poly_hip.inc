@@ -66,18 +66,27 @@ struct PolyDev {
 };
 
 struct PolyCtx {
-	PolyDev p;
+	PolyDev p; /* a view of the buffers below (freqf, tab and err: of the context's) */
+	DevBuf<uint8_t> obs, geno, z;
+	DevBuf<int> nvalid, lclass, gidoff, cnt, cnt2, cntmix2, qqnum, ccnt;
+	DevBuf<unsigned> rankwave;
+	DevBuf<unsigned long long> ambwave, accbuf;
+	DevBuf<short> gidmap;
+	std::vector<DevBuf<int>> dlists; /* the classes' genotype lists: what the device copies of isg_polyclass point to */
+	DevBuf<isg_polyclass> pc;
+	DevBuf<double> freq, lfreq, freq2, lfreq2, qq, indvlkh;
+	DevBuf<float> exfreq, genofreq, genofreqT, tabtmp;
 	std::vector<int> classes;            /* distinct allele counts, ascending */
 	std::vector<std::vector<int>> lists; /* genotype lists per class */
 	std::vector<int> lclass_h;
 	unsigned long long total_amb;
-	int *d_cntmix;
-	float *d_self; /* [2][KCAP] current and proposed selfing rates as the tables take them (float) */
-	unsigned long long *d_catcnt;
+	DevBuf<int> d_cntmix;
+	DevBuf<float> d_self; /* [2][KCAP] current and proposed selfing rates as the tables take them (float) */
+	DevBuf<unsigned long long> d_catcnt;
 	bool counts_valid; /* cnt / cntmix / ccnt / catcnt describe the current (geno, Z) */
 	bool freq_host;    /* the host mirror of freq is current (replay: drawn on the host) */
 	bool wide;         /* Amax 17..32: closed-form rows (no gidmap), k4_exfreq_w / k4_genfreq_w and the *_w sweeps */
-	float *d_zpart = nullptr; /* k4_zexpect: [N][8][2 K] partial sums */
+	DevBuf<float> d_zpart; /* k4_zexpect: [N][8][2 K] partial sums */
 	hvec<double> freq2_h; /* [K][L][Amax] second subgenome (allo) */
 	hvec<int> cnt2_h;
 	std::vector<float> tab_h;
@@ -1555,77 +1564,64 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 	memset(&d, 0, sizeof(d));
 	d.N = N; d.L = L; d.Lp = Lp; d.K = K; d.KP = KP; d.Amax = Amax; d.mode = 2; d.type_freq = 1;
 	HIPCHK(hipStreamCreate(&c->stream));
-	void *vp;
-#define DALLOC(field, type, count)                              \
-	HIPCHK(hipMalloc(&vp, sizeof(type) * (size_t)(count)));  \
-	HIPCHK(hipMemset(vp, 0, sizeof(type) * (size_t)(count))); \
-	field = (type *)vp;
-#define DUPLOAD(field, type, vec)                                                                   \
-	{                                                                                           \
-		type *tmp_;                                                                         \
-		DALLOC(tmp_, type, (vec).size());                                                   \
-		HIPCHK(hipMemcpy(tmp_, (vec).data(), sizeof(type) * (vec).size(), hipMemcpyHostToDevice)); \
-		field = tmp_;                                                                       \
-	}
-	DUPLOAD(p.obs, uint8_t, pk);
-	DALLOC(p.geno, uint8_t, (size_t)N * Lp * 4);
-	DALLOC(p.z, uint8_t, (size_t)N * Lp * 4);
-	HIPCHK(hipMemset(p.geno, 0xff, (size_t)N * Lp * 4));
-	HIPCHK(hipMemset(p.z, 0xff, (size_t)N * Lp * 4));
-	DUPLOAD(p.nvalid, int, nvalid);
-	DUPLOAD(p.rankwave, unsigned, rw);
-	DUPLOAD(p.ambwave, unsigned long long, aw);
-	DUPLOAD(p.lclass, int, pc->lclass_h);
-	DUPLOAD(p.gidmap, short, gidmap);
-	DUPLOAD(p.gidoff, int, gidoff);
+	const size_t nfreq = (size_t)Lp * Amax * KP, ncnt = (size_t)Lp * Amax * K, ntab = (size_t)K * L * GS;
+	HIPCHK(pc->obs.upload(pk));
+	HIPCHK(pc->geno.alloc_zero((size_t)N * Lp * 4));
+	HIPCHK(pc->z.alloc_zero((size_t)N * Lp * 4));
+	HIPCHK(hipMemset(pc->geno, 0xff, (size_t)N * Lp * 4));
+	HIPCHK(hipMemset(pc->z, 0xff, (size_t)N * Lp * 4));
+	HIPCHK(pc->nvalid.upload(nvalid));
+	HIPCHK(pc->rankwave.upload(rw));
+	HIPCHK(pc->ambwave.upload(aw));
+	HIPCHK(pc->lclass.upload(pc->lclass_h));
+	HIPCHK(pc->gidmap.upload(gidmap));
+	HIPCHK(pc->gidoff.upload(gidoff));
+	pc->dlists.resize(ncls);
 	for (int q = 0; q < ncls; q++) {
-		int *dl;
-		DALLOC(dl, int, pc->lists[q].size());
-		HIPCHK(hipMemcpy(dl, pc->lists[q].data(), sizeof(int) * pc->lists[q].size(), hipMemcpyHostToDevice));
-		cls[q].list = dl;
+		HIPCHK(pc->dlists[q].upload(pc->lists[q]));
+		cls[q].list = pc->dlists[q];
 	}
-	DUPLOAD(p.pc, isg_polyclass, cls);
-	DALLOC(p.freq, double, (size_t)Lp * Amax * KP);
-	DALLOC(p.lfreq, double, (size_t)Lp * Amax * KP);
-	DALLOC(p.cnt, int, (size_t)Lp * Amax * K);
+	HIPCHK(pc->pc.upload(cls));
+	HIPCHK(pc->freq.alloc_zero(nfreq));
+	HIPCHK(pc->lfreq.alloc_zero(nfreq));
+	HIPCHK(pc->cnt.alloc_zero(ncnt));
 	if (allo) {
-		DALLOC(p.freq2, double, (size_t)Lp * Amax * KP);
-		DALLOC(p.lfreq2, double, (size_t)Lp * Amax * KP);
-		DALLOC(p.cnt2, int, (size_t)Lp * Amax * K);
-		DALLOC(p.cntmix2, int, (size_t)Lp * Amax * K);
+		HIPCHK(pc->freq2.alloc_zero(nfreq));
+		HIPCHK(pc->lfreq2.alloc_zero(nfreq));
+		HIPCHK(pc->cnt2.alloc_zero(ncnt));
+		HIPCHK(pc->cntmix2.alloc_zero(ncnt));
 		pc->freq2_h.assign((size_t)K * L * Amax, 0.0);
 		pc->cnt2_h.assign((size_t)L * Amax * K, 0);
 	}
-	DALLOC(p.qq, double, (size_t)N * K);
-	DALLOC(c->d_qqsave, double, (size_t)N * K);
-	DALLOC(p.qqnum, int, (size_t)N * K);
-	DALLOC(p.indvlkh, double, N);
-	DALLOC(p.exfreq, float, (size_t)K * L * GS);
-	DALLOC(p.genofreq, float, (size_t)K * L * GS);
-	DALLOC(p.genofreqT, float, (size_t)K * GS * Lp);
-	DALLOC(p.tabtmp, float, (size_t)K * L * GS);
-	DALLOC(pc->d_self, float, 2 * ISG_KCAP);
-	DALLOC(p.ccnt, int, (size_t)K * L * GS);
-	DALLOC(p.accbuf, unsigned long long, 5 * (2 * ISG_KCAP + 2));
-	DALLOC(pc->d_cntmix, int, (size_t)Lp * Amax * K);
-	DALLOC(pc->d_catcnt, unsigned long long, 8);
+	HIPCHK(pc->qq.alloc_zero((size_t)N * K));
+	HIPCHK(c->d_qqsave.alloc_zero((size_t)N * K));
+	HIPCHK(pc->qqnum.alloc_zero((size_t)N * K));
+	HIPCHK(pc->indvlkh.alloc_zero(N));
+	HIPCHK(pc->exfreq.alloc_zero(ntab));
+	HIPCHK(pc->genofreq.alloc_zero(ntab));
+	HIPCHK(pc->genofreqT.alloc_zero((size_t)K * GS * Lp));
+	HIPCHK(pc->tabtmp.alloc_zero(ntab));
+	HIPCHK(pc->d_self.alloc_zero(2 * ISG_KCAP));
+	HIPCHK(pc->ccnt.alloc_zero(ntab));
+	HIPCHK(pc->accbuf.alloc_zero(5 * (2 * ISG_KCAP + 2)));
+	HIPCHK(pc->d_cntmix.alloc_zero(ncnt));
+	HIPCHK(pc->d_catcnt.alloc_zero(8));
+	p.obs = pc->obs; p.geno = pc->geno; p.z = pc->z; p.nvalid = pc->nvalid; p.rankwave = pc->rankwave; p.ambwave = pc->ambwave; p.lclass = pc->lclass;
+	p.gidmap = pc->gidmap; p.gidoff = pc->gidoff; p.pc = pc->pc; p.freq = pc->freq; p.lfreq = pc->lfreq; p.cnt = pc->cnt;
+	p.freq2 = pc->freq2; p.lfreq2 = pc->lfreq2; p.cnt2 = pc->cnt2; p.cntmix2 = pc->cntmix2;
+	p.qq = pc->qq; p.qqnum = pc->qqnum; p.indvlkh = pc->indvlkh; p.exfreq = pc->exfreq; p.genofreq = pc->genofreq; p.genofreqT = pc->genofreqT;
+	p.tabtmp = pc->tabtmp; p.ccnt = pc->ccnt; p.accbuf = pc->accbuf;
 	pc->counts_valid = false;
 	pc->freq_host = true;
 	d.KPF = (K + 3) & ~3;
-	DALLOC(d.freqf, float, (size_t)Lp * Amax * d.KPF);
-	p.freqf = d.freqf;
+	HIPCHK(c->d_freqf.alloc_zero((size_t)Lp * Amax * d.KPF));
+	p.freqf = d.freqf = c->d_freqf;
 	p.KPF = d.KPF;
 	{
-		CoopBuf *cbp;
-		DALLOC(cbp, CoopBuf, 1);
-		c->d_coop = cbp;
+		HIPCHK(c->d_coop.alloc_zero(1));
 		c->coop = env_flag(getenv("INSTRUCT_ZQ_COOP"), true);
 		c->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_TEST_ABORT"), 0);
 	}
-	c->d_tape = nullptr;
-	c->tape_cap = 0;
-	c->nvalid_total = 0;
-	for (int i = 0; i < N; i++) c->nvalid_total += (uint64_t)nvalid[i];
 	{ /* replay update_ZQ with the start positions resolved block-wise (k4_zq_block): opt-in for ploidy 4.  A candidate costs
 	   * 4 L draws against K - 1 thresholds and the windows widen with K: at config 5 (K = 10, L = 20000) the resolution takes
 	   * 158 ms + 8.6 ms for the sweep, the cooperative chain kernel 105 ms (INSTRUCT_ZQ_RESOLVE_P4=1 to use it anyway) */
@@ -1637,44 +1633,16 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 		if (spec_create(c, &c->zspec, nvalid, 4)) return 1;
 		if (c->zspec) {
 			c->zspec->err_bit = 8u;
-			HIPCHK(hipMalloc((void **)&pc->d_zpart, sizeof(float) * (size_t)N * K4Z_NRANGE * 2 * K));
+			HIPCHK(pc->d_zpart.alloc((size_t)N * K4Z_NRANGE * 2 * K));
 		}
 	}
-	isg_wh_tables_init(&c->tab_h);
-	isg_wh_tables *dt;
-	DALLOC(dt, isg_wh_tables, 1);
-	HIPCHK(hipMemcpy(dt, &c->tab_h, sizeof(isg_wh_tables), hipMemcpyHostToDevice));
-	p.tab = dt;
-	DALLOC(c->d_pos, uint64_t, 4);
-	DALLOC(c->d_err, unsigned, 4);
-	DALLOC(c->d_total, double, 1);
-	DALLOC(c->d_S, double, ISG_KCAP);
-	DALLOC(c->d_state, int, ISG_KCAP);
-	p.err = c->d_err;
-#undef DALLOC
-#undef DUPLOAD
-	d.freq = p.freq; d.cnt = p.cnt; d.qq = p.qq; d.qqnum = p.qqnum; d.indvlkh = p.indvlkh; d.tab = p.tab; d.err = p.err; d.nvalid = p.nvalid;
-	c->freq.assign((size_t)K * L * Amax, 0.0);
-	c->freq_stage.assign((size_t)Lp * Amax * KP, 0.0);
-	c->qq.assign((size_t)N * K, 0.0);
-	c->qqnum.assign((size_t)N * K, 0);
-	c->gen.assign(N, 0);
-	c->S.assign(K, 0.0);
-	c->state.assign(K, 0);
-	c->indvlkh.assign(N, 0.0);
-	c->cnt_h.assign((size_t)L * Amax * K, 0);
-	pin_host(c, c->cnt_h.data(), sizeof(int) * c->cnt_h.size());
-	pin_host(c, c->freq_stage.data(), sizeof(double) * c->freq_stage.size());
+	if (ctx_init_common(c, nvalid, Lp, KP, K)) return 1;
+	HIPCHK(c->d_total.alloc_zero(1));
+	HIPCHK(c->d_S.alloc_zero(ISG_KCAP));
+	HIPCHK(c->d_state.alloc_zero(ISG_KCAP));
+	p.tab = d.tab; p.err = d.err;
+	d.freq = p.freq; d.cnt = p.cnt; d.qq = p.qq; d.qqnum = p.qqnum; d.indvlkh = p.indvlkh; d.nvalid = p.nvalid;
 	if (!wide) pc->tab_h.assign((size_t)K * L * GS, 0.f);
-	c->alpha = 0;
-	c->totallkh = 0;
-	c->iter = 0;
-	c->rng.s1 = 13; c->rng.s2 = 4; c->rng.s3 = 1972;
-	c->origin = c->rng;
-	c->raw_seed[0] = 13; c->raw_seed[1] = 4; c->raw_seed[2] = 1972;
-	c->raw_valid = true;
-	c->prof = false;
-	c->h_qq = c->h_gen = c->h_S = c->h_lkh = true;
 	{ /* keyed layout, ploidy 4 (include/instruct_hip.h): the genotype sweeps take one uniform per ambiguous locus */
 		const uint64_t N64 = N, L64 = L, K64 = K, amb = pc->total_amb;
 		const uint64_t SP = (allo ? 2 : 1) * (16 * (uint64_t)Amax + 16), SZ = 4 * L64 + 16 * K64 + 16, ZI0 = 1 + amb, B0 = ZI0 + N64 * SZ;
@@ -1685,19 +1653,6 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 	guard.release();
 	*out = c;
 	return 0;
-}
-
-static void poly_ctx_destroy(isg_ctx *c)
-{
-	PolyDev &p = c->poly->p;
-	(void)hipFree((void *)p.obs); (void)hipFree(p.geno); (void)hipFree(p.z); (void)hipFree((void *)p.nvalid); (void)hipFree((void *)p.rankwave);
-	(void)hipFree((void *)p.ambwave); (void)hipFree((void *)p.lclass); (void)hipFree((void *)p.gidmap); (void)hipFree((void *)p.gidoff);
-	(void)hipFree(p.freq2); (void)hipFree(p.cnt2); (void)hipFree(p.cntmix2); (void)hipFree(p.lfreq); (void)hipFree(p.lfreq2); (void)hipFree(p.genofreqT);
-	(void)hipFree((void *)p.pc); (void)hipFree(p.freq); (void)hipFree(p.cnt); (void)hipFree(p.qq); (void)hipFree(c->d_qqsave); (void)hipFree(p.qqnum); (void)hipFree(p.indvlkh);
-	(void)hipFree(p.exfreq); (void)hipFree(p.genofreq); (void)hipFree(p.tabtmp); (void)hipFree(p.ccnt); (void)hipFree(p.accbuf); (void)hipFree((void *)p.tab);
-	(void)hipFree(c->d_pos); (void)hipFree(c->d_err); (void)hipFree(c->d_total); (void)hipFree(c->d_S); (void)hipFree(c->d_state);
-	(void)hipFree(c->d.freqf); (void)hipFree(c->d_coop); (void)hipFree(c->d_tape); (void)hipFree(c->poly->d_cntmix); (void)hipFree(c->poly->d_catcnt); (void)hipFree(c->poly->d_self); (void)hipFree(c->poly->d_zpart);
-	delete c->poly;
 }
 
 static int poly_check_err(isg_ctx *c)

@@ -73,15 +73,15 @@ extern "C" int isg_gather_convg(isg_ctx *c, int rank, int world, const char *id_
 	}
 	ncclComm_t comm;
 	NCCLCHK(api.CommInitRank(&comm, world, id, rank));
-	double *d_in = nullptr, *d_out = nullptr;
-	HIPCHK(hipMalloc((void **)&d_in, sizeof(double) * (size_t)n));
-	HIPCHK(hipMalloc((void **)&d_out, sizeof(double) * (size_t)n * world));
-	HIPCHK(hipMemcpyAsync(d_in, mine, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-	NCCLCHK(api.AllGather(d_in, d_out, (size_t)n, ncclDouble, comm, c->stream));
-	HIPCHK(hipMemcpyAsync(all, d_out, sizeof(double) * (size_t)n * world, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	(void)hipFree(d_in);
-	(void)hipFree(d_out);
+	{ /* (the buffers go before the communicator, on every way out) */
+		DevBuf<double> d_in, d_out;
+		HIPCHK(d_in.alloc((size_t)n));
+		HIPCHK(d_out.alloc((size_t)n * world));
+		HIPCHK(hipMemcpyAsync(d_in, mine, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+		NCCLCHK(api.AllGather(d_in.get(), d_out.get(), (size_t)n, ncclDouble, comm, c->stream));
+		HIPCHK(hipMemcpyAsync(all, d_out, sizeof(double) * (size_t)n * world, hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipStreamSynchronize(c->stream));
+	}
 	NCCLCHK(api.CommDestroy(comm));
 	return 0;
 }

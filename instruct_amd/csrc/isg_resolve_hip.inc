@@ -707,12 +707,12 @@ static void resolve_plan_build(ResolvePlan &p, int K, int nunits_max, double mu,
 }
 
 struct ResolveCtx {
-	unsigned long long *d_B = nullptr, *d_offs = nullptr;
-	float *d_tapef = nullptr;
-	uint64_t tapef_cap = 0;
-	ResolvePlan plan_h, *d_plan = nullptr;
-	ResolveState *d_st = nullptr;
-	unsigned long long *d_gran = nullptr; /* k_zq_blocks: [2][ISG_RS_UMAX] tagged granules, then the abort word */
+	DevBuf<unsigned long long> d_B, d_offs;
+	DevBuf<float> d_tapef;
+	ResolvePlan plan_h;
+	DevBuf<ResolvePlan> d_plan;
+	DevBuf<ResolveState> d_st;
+	DevBuf<unsigned long long> d_gran; /* k_zq_blocks: [2][ISG_RS_UMAX] tagged granules, then the abort word */
 	bool persist = true;                  /* the whole resolution in one launch (INSTRUCT_ZQ_RESOLVE_PERSIST=0: one launch per block) */
 	/* Windows: individual r of a block gets  mu r +- a_r sigma sqrt(r),  a_r = a (1 + shape (1/2 - r / 64)):  wide early, narrow late (a
 	 * walk that leaves its window at individual r wastes the block's remaining D - r).  Measured at config 3, update_ZQ's block kernel
@@ -729,15 +729,6 @@ struct ResolveCtx {
 	unsigned long long last_blocks = 0, last_miss = 0, last_launches = 0, last_exact = 0;
 };
 
-static void resolve_free(isg_ctx *c)
-{
-	ResolveCtx *r = c->rs;
-	if (!r) return;
-	(void)hipFree(r->d_B); (void)hipFree(r->d_offs); (void)hipFree(r->d_tapef); (void)hipFree(r->d_plan); (void)hipFree(r->d_st); (void)hipFree(r->d_gran);
-	delete r;
-	c->rs = nullptr;
-}
-
 /* nvalid: loci used per individual (host copy); called once per context */
 static int resolve_alloc(isg_ctx *c, const std::vector<int> &nvalid, int copies = 2, int kmax = 8)
 {
@@ -750,12 +741,12 @@ static int resolve_alloc(isg_ctx *c, const std::vector<int> &nvalid, int copies 
 	r->copies = copies;
 	std::vector<unsigned long long> B((size_t)N + 1, 0);
 	for (int i = 0; i < N; i++) B[i + 1] = B[i] + (unsigned long long)copies * (unsigned)nvalid[i] + 2ull * (unsigned)K;
-	HIPCHK(hipMalloc((void **)&r->d_B, sizeof(unsigned long long) * ((size_t)N + 1)));
+	HIPCHK(r->d_B.alloc((size_t)N + 1));
 	HIPCHK(hipMemcpy(r->d_B, B.data(), sizeof(unsigned long long) * ((size_t)N + 1), hipMemcpyHostToDevice));
-	HIPCHK(hipMalloc((void **)&r->d_offs, sizeof(unsigned long long) * ((size_t)N + 1)));
-	HIPCHK(hipMalloc((void **)&r->d_plan, sizeof(ResolvePlan)));
-	HIPCHK(hipMalloc((void **)&r->d_st, sizeof(ResolveState)));
-	HIPCHK(hipMalloc((void **)&r->d_gran, sizeof(unsigned long long) * (2 * ISG_RS_UMAX + 1)));
+	HIPCHK(r->d_offs.alloc((size_t)N + 1));
+	HIPCHK(r->d_plan.alloc(1));
+	HIPCHK(r->d_st.alloc(1));
+	HIPCHK(r->d_gran.alloc(2 * ISG_RS_UMAX + 1));
 	r->persist = env_flag(getenv("INSTRUCT_ZQ_RESOLVE_PERSIST"), true);
 	/* rejected attempts per individual: about 0.46 per gamma with a spread of 0.8 sqrt(K) (measured at K = 5: 2.3, 1.8);
 	 * replaced by the previous sweep's own statistics from the second sweep on */
@@ -817,13 +808,7 @@ static int resolve_update_ZQ_with(isg_ctx *c, isg_wh base, bool *done, LB launch
 	const int N = c->cfg.N, K = c->cfg.K;
 	/* the float image of the phase's stretch of the stream (Z draws of all individuals + Dirichlet allowance) */
 	const uint64_t need = (uint64_t)r->copies * c->nvalid_total + (uint64_t)(8 * K + 32 > 96 ? 8 * K + 32 : 96) * (uint64_t)N + 4096;
-	if (need > r->tapef_cap) {
-		if (r->d_tapef) HIPCHK(hipFree(r->d_tapef));
-		r->d_tapef = nullptr;
-		r->tapef_cap = 0;
-		HIPCHK(hipMalloc((void **)&r->d_tapef, sizeof(float) * need));
-		r->tapef_cap = need;
-	}
+	HIPCHK(r->d_tapef.grow(need));
 	prof_begin(c);
 	hipLaunchKernelGGL(k_tapef, dim3((unsigned)((need + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, base, (unsigned long long)need, r->d_tapef);
 	prof_end(c, "k_tapef");
@@ -856,7 +841,7 @@ static int resolve_update_ZQ_with(isg_ctx *c, isg_wh base, bool *done, LB launch
 		launch_at();
 		prof_end(c, "k_zq_at");
 		if (hipGetLastError() != hipSuccess) launch_failed = true; /* (resources, an occupancy other than fits_resident saw): the chain kernels take the sweep */
-		HIPCHK(hipMemcpyAsync(&hs, &r->d_st->done, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(&hs, &r->d_st.get()->done, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipMemcpyAsync(err, c->d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
 		if (hs.fail || hs.done || one || launch_failed) break; /* (k_zq_blocks ends resolved or failed) */

@@ -41,14 +41,14 @@ struct SpecCtx {
 	WalkRun walk;
 	int N = 0, K = 0, copies = 2;
 	std::vector<int> gam0_h;
-	int *d_gam0 = nullptr;
-	unsigned long long *d_gpos = nullptr, *d_B = nullptr, *d_offs = nullptr;
-	float *d_alo = nullptr, *d_ahi = nullptr;
+	DevBuf<int> d_gam0;
+	DevBuf<unsigned long long> d_gpos, d_B, d_offs;
+	DevBuf<float> d_alo, d_ahi;
 	bool zstrip = false;      /* ploidy 4, INSTRUCT_ZEXPECT_STRIP=1: the strip-per-wave kernel k4_zexpect instead of one lane per individual.  (The diploid
 	                           * k_zexpect gains nothing from a lane per individual: 0.196 against 0.190 ms at config 3, measured.) */
-	SpecProbe *d_list = nullptr;
-	SpecDev *d_dev = nullptr;
-	ResolveState *d_rs = nullptr;
+	DevBuf<SpecProbe> d_list;
+	DevBuf<SpecDev> d_dev;
+	DevBuf<ResolveState> d_rs;
 	int list_cap = 0, band = 0, rounds = 2; /* rounds launched without looking (two settle 9 sweeps in 10 at config 3; more, one by one, if not) */
 	float ksig = 4.5f;
 	unsigned err_bit = 4u;
@@ -313,15 +313,6 @@ __global__ void __launch_bounds__(256) k_zs_offs(const unsigned long long *T, co
 	}
 }
 
-static void spec_free(SpecCtx *sp)
-{
-	if (!sp) return;
-	walk_free(sp->walk);
-	(void)hipFree(sp->d_gam0); (void)hipFree(sp->d_gpos); (void)hipFree(sp->d_B); (void)hipFree(sp->d_offs); (void)hipFree(sp->d_alo); (void)hipFree(sp->d_ahi);
-	(void)hipFree(sp->d_list); (void)hipFree(sp->d_dev); (void)hipFree(sp->d_rs);
-	delete sp;
-}
-
 /* nvalid: used loci per individual (host); copies: allele copies per locus = uniforms per used locus */
 static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid, int copies)
 {
@@ -349,20 +340,20 @@ static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid
 	sp->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), sp->walk.kwin, 1.0);
 	sp->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_SPEC_TEST_ABORT"), 0);
 	sp->list_cap = 6 * N + 1024;
-	HIPCHK(hipMalloc((void **)&sp->d_gam0, sizeof(int) * ((size_t)N + 1)));
-	HIPCHK(hipMalloc((void **)&sp->d_gpos, sizeof(unsigned long long) * ((size_t)N * K + 1)));
-	HIPCHK(hipMalloc((void **)&sp->d_B, sizeof(unsigned long long) * ((size_t)N + 1)));
-	HIPCHK(hipMalloc((void **)&sp->d_offs, sizeof(unsigned long long) * ((size_t)N + 1)));
-	HIPCHK(hipMalloc((void **)&sp->d_alo, sizeof(float) * (size_t)N * K));
-	HIPCHK(hipMalloc((void **)&sp->d_ahi, sizeof(float) * (size_t)N * K));
+	*out = sp; /* the context owns it from here on, whatever fails below */
+	HIPCHK(sp->d_gam0.alloc((size_t)N + 1));
+	HIPCHK(sp->d_gpos.alloc((size_t)N * K + 1));
+	HIPCHK(sp->d_B.alloc((size_t)N + 1));
+	HIPCHK(sp->d_offs.alloc((size_t)N + 1));
+	HIPCHK(sp->d_alo.alloc((size_t)N * K));
+	HIPCHK(sp->d_ahi.alloc((size_t)N * K));
 	sp->zstrip = env_flag(getenv("INSTRUCT_ZEXPECT_STRIP"), false);
-	HIPCHK(hipMalloc((void **)&sp->d_list, sizeof(SpecProbe) * (size_t)sp->list_cap));
-	HIPCHK(hipMalloc((void **)&sp->d_dev, sizeof(SpecDev)));
-	HIPCHK(hipMalloc((void **)&sp->d_rs, sizeof(ResolveState)));
+	HIPCHK(sp->d_list.alloc((size_t)sp->list_cap));
+	HIPCHK(sp->d_dev.alloc(1));
+	HIPCHK(sp->d_rs.alloc(1));
 	HIPCHK(hipMemcpy(sp->d_gam0, sp->gam0_h.data(), sizeof(int) * ((size_t)N + 1), hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(sp->d_gpos, gpos.data(), sizeof(unsigned long long) * gpos.size(), hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(sp->d_B, B.data(), sizeof(unsigned long long) * B.size(), hipMemcpyHostToDevice));
-	*out = sp;
 	return 0;
 }
 
@@ -408,7 +399,7 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 		prof_begin(c);
 		launch_probe(1024);
 		prof_end(c, "k_zq_probe");
-		(void)hipMemsetAsync((char *)w.d_st + offsetof(WkState, sum_d), 0, sizeof(WkState) - offsetof(WkState, sum_d), c->stream);
+		(void)hipMemsetAsync((char *)w.d_st.get() + offsetof(WkState, sum_d), 0, sizeof(WkState) - offsetof(WkState, sum_d), c->stream);
 		for (int s = 0; s < nseg; s++) walk_launch_walk(c, w, in, s, 0, 1, "k_wk_walk_Z");
 		list_on_path();
 	};
@@ -429,7 +420,7 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 	WkState hs;
 	SpecDev hd;
 	unsigned err[4] = {0, 0, 0, 0};
-	HIPCHK(hipMemcpyAsync(&hr, &sp->d_rs->done, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(&hr, &sp->d_rs.get()->done, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipMemcpyAsync(&hs, w.d_st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipMemcpyAsync(&hd, sp->d_dev, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipMemcpyAsync(err, c->d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
@@ -438,7 +429,7 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 		round();
 		finish();
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(&hr, &sp->d_rs->done, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(&hr, &sp->d_rs.get()->done, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipMemcpyAsync(&hs, w.d_st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipMemcpyAsync(&hd, sp->d_dev, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipMemcpyAsync(err, c->d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));

@@ -69,17 +69,15 @@ struct WalkRun {
 	WkPlan plan;
 	bool plan_ok = false, attrs_set = false;
 	int mode = WK_MODE_EXACT;
-	WkBlock *d_blk = nullptr;
-	WkSuper *d_sup = nullptr;
-	WkSeg *d_seg = nullptr;
-	int *d_hw = nullptr, *d_ent_sup = nullptr, *d_ent_blk = nullptr;
-	float *d_bpred = nullptr;
-	unsigned char *d_table = nullptr;
-	unsigned short *d_maps = nullptr;
-	size_t table_cap = 0, maps_cap = 0, nblk_cap = 0, nsup_cap = 0;
-	unsigned long long *d_T = nullptr;
-	size_t T_cap = 0;
-	WkState *d_st = nullptr;
+	DevBuf<WkBlock> d_blk;
+	DevBuf<WkSuper> d_sup;
+	DevBuf<WkSeg> d_seg;
+	DevBuf<int> d_hw, d_ent_sup, d_ent_blk;
+	DevBuf<float> d_bpred;
+	DevBuf<unsigned char> d_table;
+	DevBuf<unsigned short> d_maps;
+	DevBuf<unsigned long long> d_T;
+	DevBuf<WkState> d_st;
 	/* window statistics, carried from run to run */
 	double sigma = 1.0, kwin = 4.0, rho_hi = 0.8; /* windows of +-kwin sigma sqrt(gammas): a miss (6e-5 per entry at 4 sigma) costs one sweep by the other path */
 	double kwin0 = 0.0; /* what kwin returns to after a clean stretch */
@@ -90,13 +88,6 @@ struct WalkRun {
 	int plan_seg_groups = 0, plan_slack = 0; /* what the current plan was built for */
 	long runs = 0, fails = 0;
 };
-
-static void walk_free(WalkRun &w)
-{
-	(void)hipFree(w.d_blk); (void)hipFree(w.d_sup); (void)hipFree(w.d_hw); (void)hipFree(w.d_ent_sup); (void)hipFree(w.d_ent_blk); (void)hipFree(w.d_bpred);
-	(void)hipFree(w.d_table); (void)hipFree(w.d_maps); (void)hipFree(w.d_T); (void)hipFree(w.d_st); (void)hipFree(w.d_seg);
-	w = WalkRun();
-}
 
 /* (re)builds the plan for the current window statistics and makes the buffers fit; false: the run does not fit the engine */
 static int walk_prepare(isg_ctx *c, WalkRun &w, const int *gam0_h, int G, int mode, bool reuse, bool *ok, int entry_slack = 0)
@@ -118,47 +109,17 @@ static int walk_prepare(isg_ctx *c, WalkRun &w, const int *gam0_h, int G, int mo
 		/* the old plan may still be in use by kernels of the previous sweep */
 		HIPCHK(hipStreamSynchronize(c->stream));
 		w.plan = np;
-		if (np.blk.size() > w.nblk_cap) {
-			(void)hipFree(w.d_blk); (void)hipFree(w.d_hw); (void)hipFree(w.d_ent_blk); (void)hipFree(w.d_bpred);
-			w.d_blk = nullptr; w.d_hw = nullptr; w.d_ent_blk = nullptr; w.d_bpred = nullptr;
-			w.nblk_cap = 0;
-			HIPCHK(hipMalloc((void **)&w.d_blk, sizeof(WkBlock) * np.blk.size()));
-			HIPCHK(hipMalloc((void **)&w.d_hw, sizeof(int) * np.blk.size()));
-			HIPCHK(hipMalloc((void **)&w.d_ent_blk, sizeof(int) * np.blk.size()));
-			HIPCHK(hipMalloc((void **)&w.d_bpred, sizeof(float) * np.blk.size()));
-			w.nblk_cap = np.blk.size();
-		}
-		if (np.sup.size() > w.nsup_cap) {
-			(void)hipFree(w.d_sup); (void)hipFree(w.d_ent_sup);
-			w.d_sup = nullptr; w.d_ent_sup = nullptr;
-			w.nsup_cap = 0;
-			HIPCHK(hipMalloc((void **)&w.d_sup, sizeof(WkSuper) * np.sup.size()));
-			HIPCHK(hipMalloc((void **)&w.d_ent_sup, sizeof(int) * np.sup.size()));
-			w.nsup_cap = np.sup.size();
-		}
-		if (np.table_bytes + 64 > w.table_cap) {
-			(void)hipFree(w.d_table);
-			w.d_table = nullptr;
-			w.table_cap = 0;
-			HIPCHK(hipMalloc((void **)&w.d_table, np.table_bytes + 64));
-			w.table_cap = np.table_bytes + 64;
-		}
-		if (np.maps_elems + 64 > w.maps_cap) {
-			(void)hipFree(w.d_maps);
-			w.d_maps = nullptr;
-			w.maps_cap = 0;
-			HIPCHK(hipMalloc((void **)&w.d_maps, sizeof(unsigned short) * (np.maps_elems + 64)));
-			w.maps_cap = np.maps_elems + 64;
-		}
-		if ((size_t)G + 1 > w.T_cap) {
-			(void)hipFree(w.d_T);
-			w.d_T = nullptr;
-			w.T_cap = 0;
-			HIPCHK(hipMalloc((void **)&w.d_T, sizeof(unsigned long long) * ((size_t)G + 1)));
-			w.T_cap = (size_t)G + 1;
-		}
-		if (!w.d_st) HIPCHK(hipMalloc((void **)&w.d_st, sizeof(WkState)));
-		if (!w.d_seg) HIPCHK(hipMalloc((void **)&w.d_seg, sizeof(WkSeg) * WK_MAXSEG));
+		HIPCHK(w.d_blk.grow(np.blk.size()));
+		HIPCHK(w.d_hw.grow(np.blk.size()));
+		HIPCHK(w.d_ent_blk.grow(np.blk.size()));
+		HIPCHK(w.d_bpred.grow(np.blk.size()));
+		HIPCHK(w.d_sup.grow(np.sup.size()));
+		HIPCHK(w.d_ent_sup.grow(np.sup.size()));
+		HIPCHK(w.d_table.grow(np.table_bytes + 64));
+		HIPCHK(w.d_maps.grow(np.maps_elems + 64));
+		HIPCHK(w.d_T.grow((size_t)G + 1));
+		if (!w.d_st) HIPCHK(w.d_st.alloc(1));
+		if (!w.d_seg) HIPCHK(w.d_seg.alloc(WK_MAXSEG));
 		{ /* through one page-aligned staging block (see PageAlloc): the plan's own vectors sit anywhere in the heap */
 			const size_t b0 = sizeof(WkSeg) * np.seg.size(), b1 = sizeof(WkBlock) * np.blk.size(), b2 = sizeof(WkSuper) * np.sup.size(), b3 = sizeof(int) * np.hw.size();
 			const size_t o1 = (b0 + 63) & ~(size_t)63, o2 = o1 + ((b1 + 63) & ~(size_t)63), o3 = o2 + ((b2 + 63) & ~(size_t)63);
@@ -281,12 +242,12 @@ struct PDevCtx {
 	WalkRun walk;
 	int G = 0, NG = 0;          /* groups = (cluster, locus with more than one allele) in stream order; gammas */
 	std::vector<int> gam0_h;
-	int *d_gam0 = nullptr;      /* [G + 1] */
-	int *d_gidx = nullptr;      /* [NG] index of a gamma's count in d.cnt ([L][Amax][K]) */
-	int *d_gcnt = nullptr;      /* [NG] its count */
-	unsigned long long *d_gpos = nullptr; /* [NG + 1] */
-	unsigned *d_part = nullptr; /* k_pd_gather's totals per chunk of 1024 gammas */
-	float *d_tapef = nullptr;   /* the run's uniforms as floats */
+	DevBuf<int> d_gam0;      /* [G + 1] */
+	DevBuf<int> d_gidx;      /* [NG] index of a gamma's count in d.cnt ([L][Amax][K]) */
+	DevBuf<int> d_gcnt;      /* [NG] its count */
+	DevBuf<unsigned long long> d_gpos; /* [NG + 1] */
+	DevBuf<unsigned> d_part; /* k_pd_gather's totals per chunk of 1024 gammas */
+	DevBuf<float> d_tapef;   /* the run's uniforms as floats */
 	unsigned long long tape_len = 0;
 	bool usable = false;
 	long sweeps = 0, fallbacks = 0, retried = 0; /* retried: sweeps whose tables were built a second time, with wider windows, after a missed one */
@@ -370,14 +331,6 @@ __global__ void __launch_bounds__(128) k_pdirich_at(DevView d, isg_wh base, cons
 	if ((unsigned long long)c.used != p1 - p) atomicOr(&st->fail, 8u);
 }
 
-static void pdev_free(PDevCtx *p)
-{
-	if (!p) return;
-	walk_free(p->walk);
-	(void)hipFree(p->d_gam0); (void)hipFree(p->d_gidx); (void)hipFree(p->d_gcnt); (void)hipFree(p->d_gpos); (void)hipFree(p->d_part); (void)hipFree(p->d_tapef);
-	delete p;
-}
-
 /* groups in the reference's order: for k < K, for j < L with allelenum[j] > min_alleles (mcmc.c:846-857 skips allelenum <= 1;
  * update_P_auto, poly_geno.c:426-434, does not), the alleles of (k, j); `sub` subgenomes per (k, j) (allotetraploid: 2, counts at
  * cnt and cnt + sub_stride) */
@@ -401,17 +354,17 @@ static int pdev_create(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const 
 	if (p->G < 1) { delete p; return 0; }
 	p->walk.seg_groups = (int)env_int(getenv("INSTRUCT_WALK_SEG"), 12800, 64, INT_MAX); /* (config 3's 25000 groups: two segments, measured best of 4096 .. 25600; config 5 does not care) */
 	p->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), p->walk.kwin, 1.0);
-	HIPCHK(hipMalloc((void **)&p->d_gam0, sizeof(int) * (p->G + 1)));
-	HIPCHK(hipMalloc((void **)&p->d_gidx, sizeof(int) * p->NG));
-	HIPCHK(hipMalloc((void **)&p->d_gcnt, sizeof(int) * p->NG));
-	HIPCHK(hipMalloc((void **)&p->d_gpos, sizeof(unsigned long long) * (p->NG + 1)));
-	HIPCHK(hipMalloc((void **)&p->d_part, sizeof(unsigned) * ((size_t)(p->NG + 1023) / 1024 + 2)));
+	*out = p; /* the context owns it from here on, whatever fails below (usable only at the end) */
+	HIPCHK(p->d_gam0.alloc((size_t)p->G + 1));
+	HIPCHK(p->d_gidx.alloc(p->NG));
+	HIPCHK(p->d_gcnt.alloc(p->NG));
+	HIPCHK(p->d_gpos.alloc((size_t)p->NG + 1));
+	HIPCHK(p->d_part.alloc((size_t)(p->NG + 1023) / 1024 + 2));
 	p->tape_len = 2ull * (unsigned long long)p->NG + (unsigned long long)(1.7 * p->NG) + (unsigned long long)(12.0 * sqrt((double)p->NG)) + 8192ull;
-	HIPCHK(hipMalloc((void **)&p->d_tapef, sizeof(float) * p->tape_len));
+	HIPCHK(p->d_tapef.alloc(p->tape_len));
 	HIPCHK(hipMemcpy(p->d_gam0, p->gam0_h.data(), sizeof(int) * (p->G + 1), hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(p->d_gidx, gidx.data(), sizeof(int) * p->NG, hipMemcpyHostToDevice));
 	p->usable = true;
-	*out = p;
 	return 0;
 }
 
