@@ -2151,9 +2151,9 @@ static int poly_get_bytes(isg_ctx *c, const uint8_t *dev, int32_t *out)
 }
 
 /* ------------------------------------------------------------------------------------------ */
-/* k4_zq_coop: update_ZQ with several workgroups per individual (see k_zq_coop in isg_hip.hip:   */
-/* same exchange of counts, same Dirichlet in every workgroup, same uniform tape; one locus =    */
-/* 4 allele copies per lane)                                                                     */
+/* k4_zq_coop: update_ZQ with several workgroups per individual (see k_zq_coop in               */
+/* isg_coop_hip.inc: same exchange of counts, same Dirichlet in every workgroup, same uniform    */
+/* tape; one locus = 4 allele copies per lane)                                                   */
 /* ------------------------------------------------------------------------------------------ */
 template <int KMAX, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) k4_zq_coop(PolyDev p, DevView d, isg_wh base, int init_flag, double alpha, CoopBuf *cb, uint64_t *pos_out)
@@ -2178,9 +2178,9 @@ __global__ void __launch_bounds__(BLOCK) k4_zq_coop(PolyDev p, DevView d, isg_wh
 	const int stride = G * BLOCK;
 	const size_t rowb = (size_t)p.Lp * 4;
 	const bool writer = (g == 0) && (t >= BLOCK - 64);
-	const bool wmode = (G * (BLOCK / 64) * ((K + 2) / 3) <= BLOCK);
-	const int npass = (p.Lp + G * BLOCK - 1) / (G * BLOCK);
-	const int pack = (!wmode && 4 * BLOCK * npass < 4096) ? 4 : 3, bits = (pack == 4) ? 12 : 16, W = (K + pack - 1) / pack;
+	const CoopLayout lay = coop_layout(G, BLOCK, K, p.Lp, 4); /* isg_coop_layout.h */
+	const bool wmode = lay.wmode;
+	const int pack = lay.pack, bits = lay.bits, W = lay.W;
 	double icum[KMAX];
 #pragma unroll
 	for (int m = 0; m < KMAX; m++) icum[m] = (m < K) ? (double)(m + 1) / K : 0.0;
@@ -2323,7 +2323,7 @@ __global__ void __launch_bounds__(BLOCK) k4_zq_coop(PolyDev p, DevView d, isg_wh
 		fetch_rows(g * BLOCK + t);
 		if (covered && i + 1 < p.N && lane_id() < 18) touch2 = d.tape[offi + 4ull * (unsigned)nvalid + 4ull * prw + 16u * lane_id()];
 		if (!covered && t == 0) cb->overflow_flag = 1;
-		const int ngran = wmode ? G * (BLOCK / 64) * W : G * W;
+		const int ngran = lay.ngran;
 		for (int gi = t; gi - t < ngran; gi += BLOCK) { /* wave-uniform trip count */
 			if (gi < ngran && (wmode || gi / W != g)) {
 				const unsigned long long v = coop_poll(&cb->gran[slot][gi], tag, cb);

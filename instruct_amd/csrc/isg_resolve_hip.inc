@@ -3,7 +3,7 @@
  *
  * In the replay schedule individual i+1 starts where individual i's Dirichlet (random.c:264-280, rejection samplers
  * :167-250) stopped, so the start positions form a recurrence  off[i+1] = off[i] + 2 nvalid[i] + used_i(off[i]).  The
- * kernels in isg_hip.hip walk that recurrence one individual per inter-workgroup hand-off (3.9 us each at config 3).
+ * kernels in isg_coop_hip.inc walk that recurrence one individual per inter-workgroup hand-off (3.9 us each at config 3).
  * Here the recurrence is RESOLVED first, a block of individuals at a time on the whole chip, and the sweep itself
  * (Z draws, counts, qq) is then one parallel pass over all individuals at their known positions:
  *
@@ -29,7 +29,8 @@
  * k_zq_at then runs the sweep proper, one workgroup per individual at off[i] (the keyed schedule's kernel body), and checks
  * that every Dirichlet consumed exactly what the resolution said.  Anything irregular -- a shape of exactly 1 (odd
  * consumption), more than 250 rejections, a check that fails, a wait that timed out -- makes the host redo the sweep with the
- * chain kernels of isg_hip.hip from the saved state.  Same Z, counts, qq and stream position in every case.
+ * chain kernels (isg_coop_hip.inc; the chain form of k_zq in isg_hip.hip) from the saved state.  Same Z, counts, qq and
+ * stream position in every case.
  */
 #define ISG_RS_CH 4     /* candidates per unit = waves per workgroup (one Dirichlet per wave) */
 #define ISG_RS_UMAX 512 /* units per block (workgroups of the launch) */
