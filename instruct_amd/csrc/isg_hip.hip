@@ -33,7 +33,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <array>
 #include <atomic>
 #include <chrono>
 #include <string>
@@ -45,6 +44,7 @@
 #include "isg_math.h"
 #include "isg_wh.h"
 #include "isg_sampler.h"
+#include "isg_host_dirichlet.h"
 #include "isg_kdispatch.h"
 #include "isg_devbuf.h"
 
@@ -191,7 +191,6 @@ struct isg_ctx : CtxBufs {
 	hvec<int> cnt_h;     /* device order [L][Amax][K] */
 	hvec<double> freq_stage; /* device order [L][Amax][KP] */
 	double alpha, totallkh;
-	bool qq_dirty_host;         /* host qq newer than device */
 	/* stream */
 	isg_wh rng;                 /* current sequential state (replay) */
 	isg_wh origin;              /* chain origin (keyed) */
@@ -213,9 +212,8 @@ struct isg_ctx : CtxBufs {
 	std::vector<void *> pinned;           /* host vectors registered with the runtime (pin_host): the per-sweep copies of update_P */
 	bool ahead_valid = false;             /* counts and tape of the NEXT update_P were requested at the end of update_alpha ... */
 	isg_wh ahead_rng;                     /* ... for this stream position (Z unchanged since: every writer of Z clears the flag) */
-	uint64_t ahead_ngamma = 0;
 	std::vector<double> pshape;           /* ... the shapes of its gammas in stream order ... */
-	std::vector<std::array<double, 5>> pcoef; /* ... and rgamma2's shape-only constants (HostGammaCoef) */
+	std::vector<HostGammaCoef> pcoef;     /* ... and rgamma2's shape-only constants */
 	uint64_t htape_len = 0;
 	int host_tape = 1;                    /* INSTRUCT_HOST_TAPE=0: the host loop steps the generator itself */
 	int spop_tree = 1;                    /* INSTRUCT_SPOP_TREE=0: the one-workgroup k_spop always */
@@ -1918,134 +1916,14 @@ static void host_seek(isg_ctx *c, uint64_t pos) { c->rng = isg_wh_jump(&c->tab_h
 static void host_advance(isg_ctx *c, uint64_t n) { c->rng = isg_wh_jump(&c->tab_h, c->rng, n); c->raw_valid = false; }
 
 /*
- * Host side of update_P in the replay schedule (the K L Dirichlets are drawn in stream order): rdirich
- * (random.c:264-280) with the accept / reject test of rgamma2 (random.c:195-231) pre-decided in single precision,
- * exactly as rgamma2_try_dev does on the device -- the two logarithms only feed the comparison
- * c3 log(u1) - log(w) + w >= 1; outside a band of 2e-6 (1 + |terms|) the float value decides, inside it the double
- * expression.  Same values, same consumption as isg_rdirich.
+ * The uniforms of the host's Dirichlet loop come from the device (HostTape, isg_host_dirichlet.h): k_tape writes the next
+ * host_tape_need(ngamma) uniforms of the stream and they are copied into the pinned c->htape; c->htape_len == 0: no tape this sweep.
  */
-static inline double host_rgamma2_try(isg_cursor *c, double alpha)
+static int host_tape_begin(isg_ctx *c, uint64_t ngamma)
 {
-	double u1, u2, c1, c2, c3, c4, c5, w;
-	c1 = alpha - 1;
-	c2 = (alpha - 1 / (6 * alpha)) / c1;
-	c3 = 2 / c1;
-	c4 = c3 + 2;
-	c5 = 1 / isg_sqrt(alpha);
-	do {
-		u1 = isg_cur_next(c);
-		u2 = isg_cur_next(c);
-		if (alpha > 2.5) u1 = u2 + c5 * (1 - 1.86 * u1);
-	} while ((u1 >= 1) || (u1 <= 0));
-	w = c2 * u2 / u1;
-	if ((c3 * u1 + w + 1 / w) > c4) {
-		const float l1 = logf((float)u1), lw = logf((float)w);
-		const double al1 = fabs((double)l1), alw = fabs((double)lw);
-		const double dlt = (c3 * (double)l1 - (double)lw + w) - 1;
-		const double tol = 2e-6 * (fabs(c3) * (1.0 + al1) + 1.0 + alw) + 1e-12 * fabs(w);
-		bool rej;
-		if (dlt > tol) rej = true;
-		else if (dlt < -tol) rej = false;
-		else rej = (c3 * isg_log(u1) - isg_log(w) + w) >= 1;
-		if (rej) return -1;
-	}
-	return c1 * w;
-}
-/* rgamma2's constants only depend on the shape (random.c:199-203): the sequential loop has three divisions and a square root
- * less per attempt when they are formed beforehand -- for all gammas of the sweep at once, by a few threads (the shapes are
- * the counts + 1, known before the first draw).  Same expressions, same values. */
-struct HostGammaCoef { double c1, c2, c3, c4, c5; };
-static inline void host_gamma_coef(double alpha, HostGammaCoef *o)
-{
-	o->c1 = alpha - 1;
-	o->c2 = (alpha - 1 / (6 * alpha)) / o->c1;
-	o->c3 = 2 / o->c1;
-	o->c4 = o->c3 + 2;
-	o->c5 = 1 / isg_sqrt(alpha);
-}
-static void host_gamma_coefs(const double *shape, size_t n, HostGammaCoef *out)
-{
-	unsigned nt = std::thread::hardware_concurrency();
-	nt = nt > 4 ? 4 : (nt < 1 ? 1 : nt);
-	if (n < 16384) nt = 1;
-	auto work = [&](size_t a, size_t b) { for (size_t g = a; g < b; g++) host_gamma_coef(shape[g], &out[g]); };
-	std::vector<std::thread> th;
-	const size_t per = (n + nt - 1) / nt;
-	for (unsigned k = 1; k < nt; k++) th.emplace_back(work, k * per < n ? k * per : n, (k + 1) * per < n ? (k + 1) * per : n);
-	work(0, per < n ? per : n);
-	for (auto &t : th) t.join();
-}
-static inline double host_rgamma2_try_pre(isg_cursor *c, double alpha, const HostGammaCoef &k)
-{
-	double u1, u2, w;
-	do {
-		u1 = isg_cur_next(c);
-		u2 = isg_cur_next(c);
-		if (alpha > 2.5) u1 = u2 + k.c5 * (1 - 1.86 * u1);
-	} while ((u1 >= 1) || (u1 <= 0));
-	w = k.c2 * u2 / u1;
-	if ((k.c3 * u1 + w + 1 / w) > k.c4) {
-		const float l1 = logf((float)u1), lw = logf((float)w);
-		const double al1 = fabs((double)l1), alw = fabs((double)lw);
-		const double dlt = (k.c3 * (double)l1 - (double)lw + w) - 1;
-		const double tol = 2e-6 * (fabs(k.c3) * (1.0 + al1) + 1.0 + alw) + 1e-12 * fabs(w);
-		bool rej;
-		if (dlt > tol) rej = true;
-		else if (dlt < -tol) rej = false;
-		else rej = (k.c3 * isg_log(u1) - isg_log(w) + w) >= 1;
-		if (rej) return -1;
-	}
-	return k.c1 * w;
-}
-/* rdirich over shapes given directly (count + 1 already formed) with their constants */
-static void host_rdirich_pre(isg_cursor *c, const double *shape, const HostGammaCoef *coef, int n, double *out)
-{
-	double sum = 0;
-	for (int k = 0; k < n; k++) {
-		const double a = shape[k];
-		double g = 0;
-		if (a > 1) {
-			do { g = host_rgamma2_try_pre(c, a, coef[k]); } while (g < 0);
-		} else {
-			g = isg_rgamma(c, a);
-		}
-		out[k] = g;
-		sum += g;
-	}
-	for (int k = 0; k < n; k++) out[k] /= sum;
-}
-static void host_rdirich(isg_cursor *c, const double *count, int n, double *out, double add)
-{
-	double sum = 0;
-	for (int k = 0; k < n; k++) {
-		const double a = count[k] + add;
-		double g = 0;
-		if (a > 1) {
-			do { g = host_rgamma2_try(c, a); } while (g < 0);
-		} else {
-			g = isg_rgamma(c, a);
-		}
-		out[k] = g;
-		sum += g;
-	}
-	for (int k = 0; k < n; k++) out[k] /= sum;
-}
-
-/*
- * The uniforms of the host's Dirichlet loop come from the device: half of that loop's time was the generator
- * (21 ns per uniform, ~3 per gamma of ~118 ns).  k_tape writes the next `need` uniforms of the stream, the loop reads
- * them through the cursor's tape; if they run out (they are budgeted at 3 per gamma) the loop continues with the
- * generator from the position reached -- same values either way.
- */
-__global__ void __launch_bounds__(256) k_tape(const isg_wh_tables *tab, isg_wh base, unsigned long long n, double *tape);
-static int host_tape_begin(isg_ctx *c, uint64_t ngamma, isg_cursor *cur)
-{
-	cur->s = c->rng;
-	cur->used = 0;
-	cur->tape = nullptr;
 	c->htape_len = 0;
-	if (!c->host_tape || ngamma < 4096) return 0;
-	const uint64_t need = 3 * ngamma + 65536;
+	const uint64_t need = host_tape_need(ngamma, c->host_tape != 0);
+	if (!need) return 0;
 	HIPCHK(c->d_tape.grow(need));
 	HIPCHK(c->htape.grow(need));
 	prof_begin(c);
@@ -2063,34 +1941,62 @@ static void pin_host(isg_ctx *c, void *ptr, size_t bytes)
 	if (ptr && bytes && hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess) c->pinned.push_back(ptr);
 	else (void)hipGetLastError();
 }
-/* replay update_P: marks / waits for the point of the stream where the counts' copy ends, so that the host can form the shapes and
- * their constants while the uniform tape is generated and copied */
 #define HOST_T(c, k, t0) do { if ((c)->host_timing) { const auto t1_ = std::chrono::steady_clock::now(); (c)->host_t[k] += std::chrono::duration<double>(t1_ - (t0)).count(); (t0) = t1_; } } while (0)
-static int counts_mark(isg_ctx *c)
+/*
+ * The sequential host loop of replay update_P, for every kind of chain (diploid; autotetraploid; allotetraploid: `second` gives the
+ * second subgenome's arrays): c->freq (and second->freq_h) drawn from the counts the caller's kernels left on the device, c->rng
+ * moved past the draws.  Its two halves, in the order of their stream operations and synchronisations:
+ *
+ *   HOSTP_REQUEST  1. copy of the counts to the host (first subgenome's, then the second's), behind the caller's count kernels
+ *                  2. event ev_cnt recorded: the counts have arrived
+ *                  3. k_tape and the copy of its uniforms to the host (host_tape_begin; sweeps of 4096 gammas and more)
+ *                  4. only when the draw is not part of the same call: event ev_tape recorded, the request noted in c->ahead_*
+ *   HOSTP_DRAW     5. wait for ev_cnt; the shapes, then their constants, on the host while the tape is generated and copied
+ *                  6. wait for the tape: for ev_tape when the request was made ahead (not for the stream: the previous iteration's
+ *                     cal_lkh may still be running on it), for the stream otherwise
+ *                  7. the draws
+ *
+ * The caller transposes and uploads the frequencies.  Stages of INSTRUCT_HOST_TIMING=1: 0 until the counts have arrived (steps 1-5's
+ * wait), 1 the shapes, 2 the constants, 3 step 6, 4 step 7, 5 the caller's upload.
+ */
+enum { HOSTP_REQUEST = 1, HOSTP_DRAW = 2 };
+struct HostPSecond { const int *d_cnt; int *cnt_h; double *freq_h; };
+static int host_update_P(isg_ctx *c, int halves, const int *d_cnt, const HostPSecond *second, bool skip_single)
 {
-	if (!c->ev_cnt) HIPCHK(hipEventCreateWithFlags(&c->ev_cnt.e, hipEventDisableTiming));
-	HIPCHK(hipEventRecord(c->ev_cnt, c->stream));
-	return 0;
-}
-static int counts_wait(isg_ctx *c)
-{
-	HIPCHK(hipEventSynchronize(c->ev_cnt));
-	return 0;
-}
-/* call after the stream has been synchronised, before the loop */
-static void host_tape_attach(isg_ctx *c, isg_cursor *cur) { if (c->htape_len) cur->tape = c->htape; }
-/* before each Dirichlet of n gammas: leave the tape while a comfortable margin remains (32 attempts per gamma) */
-static inline void host_tape_guard(isg_ctx *c, isg_cursor *cur, int n)
-{
-	if (cur->tape && (uint64_t)cur->used + 64ull * (unsigned)n + 64 > c->htape_len) {
-		cur->s = isg_wh_jump(&c->tab_h, c->rng, cur->used);
-		cur->tape = nullptr;
+	auto ht0 = std::chrono::steady_clock::now();
+	const HostDirichletPass pass = {c->allelenum.data(), c->cfg.K, c->cfg.L, c->Amax, skip_single, second ? 2 : 1,
+					{c->cnt_h.data(), second ? second->cnt_h : nullptr}, {c->freq.data(), second ? second->freq_h : nullptr}};
+	const uint64_t ngamma = ngamma_of(pass);
+	if (halves & HOSTP_REQUEST) {
+		HIPCHK(hipMemcpyAsync(c->cnt_h.data(), d_cnt, sizeof(int) * c->cnt_h.size(), hipMemcpyDeviceToHost, c->stream));
+		if (second) HIPCHK(hipMemcpyAsync(second->cnt_h, second->d_cnt, sizeof(int) * c->cnt_h.size(), hipMemcpyDeviceToHost, c->stream));
+		if (!c->ev_cnt) HIPCHK(hipEventCreateWithFlags(&c->ev_cnt.e, hipEventDisableTiming));
+		HIPCHK(hipEventRecord(c->ev_cnt, c->stream));
+		if (host_tape_begin(c, ngamma)) return 1;
+		if (!(halves & HOSTP_DRAW)) {
+			if (!c->ev_tape) HIPCHK(hipEventCreateWithFlags(&c->ev_tape.e, hipEventDisableTiming));
+			HIPCHK(hipEventRecord(c->ev_tape, c->stream));
+			c->ahead_rng = c->rng;
+			c->ahead_valid = true;
+			return 0;
+		}
 	}
-}
-static void host_tape_end(isg_ctx *c, isg_cursor *cur)
-{
-	c->rng = cur->tape ? isg_wh_jump(&c->tab_h, c->rng, cur->used) : cur->s;
+	HIPCHK(hipEventSynchronize(c->ev_cnt));
+	HOST_T(c, 0, ht0); /* launches + wait for the counts */
+	c->pshape.resize(ngamma);
+	c->pcoef.resize(ngamma);
+	host_pass_shapes(pass, c->pshape.data());
+	HOST_T(c, 1, ht0); /* shapes */
+	host_gamma_coefs(c->pshape.data(), (size_t)ngamma, c->pcoef.data());
+	HOST_T(c, 2, ht0); /* constants */
+	if (halves & HOSTP_REQUEST) HIPCHK(hipStreamSynchronize(c->stream));
+	else HIPCHK(hipEventSynchronize(c->ev_tape));
+	HOST_T(c, 3, ht0); /* wait for the tape */
+	const HostTape tape = {c->htape, c->htape_len, c->rng, &c->tab_h};
+	c->rng = host_pass_draw(pass, c->pshape.data(), c->pcoef.data(), tape);
 	c->raw_valid = false;
+	HOST_T(c, 4, ht0); /* the sequential draws */
+	return 0;
 }
 
 extern "C" const char *isg_last_error(void) { return g_err.c_str(); }
@@ -2165,6 +2071,8 @@ static int ctx_init_common(isg_ctx *c, const std::vector<int> &nvalid, int Lp, i
 	c->raw_seed[0] = 13; c->raw_seed[1] = 4; c->raw_seed[2] = 1972;
 	c->raw_valid = true;
 	c->prof = false;
+	c->host_timing = env_flag(getenv("INSTRUCT_HOST_TIMING"), false);
+	c->host_tape = env_flag(getenv("INSTRUCT_HOST_TAPE"), true);
 	c->h_qq = c->h_gen = c->h_S = c->h_lkh = true;
 	isg_wh_tables_init(&c->tab_h);
 	HIPCHK(c->d_tab.upload(&c->tab_h, 1));
@@ -2197,7 +2105,6 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	isg_ctx *c = new isg_ctx(); /* value-initialised: every pointer starts null */
 	c->cfg = *cfg;
 	ctx_count(c, +1);
-	c->host_timing = env_flag(getenv("INSTRUCT_HOST_TIMING"), false);
 	memset(&c->d, 0, sizeof(c->d));
 	CtxGuard guard(c); /* any early return below releases what has been allocated so far */
 	const int N = cfg->N, L = cfg->L, K = cfg->K;
@@ -2278,7 +2185,6 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 		c->spec = env_flag(getenv("INSTRUCT_ZQ_SPEC"), true);
 		c->xcd = env_flag(getenv("INSTRUCT_ZQ_XCD"), false); /* experimental, off by default: measured gain at config 3 is within noise */
 		c->pipe = env_flag(getenv("INSTRUCT_ZQ_PIPE"), true);
-		c->host_tape = env_flag(getenv("INSTRUCT_HOST_TAPE"), true);
 		c->spop_tree = env_flag(getenv("INSTRUCT_SPOP_TREE"), true);
 		c->pipe_xcd = env_flag(getenv("INSTRUCT_ZQ_PIPE_XCD"), true);
 		c->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_TEST_ABORT"), 0);
@@ -2337,9 +2243,7 @@ extern "C" int isg_keyed_layout(isg_ctx *c, uint64_t out[9])
 static int upload_freq(isg_ctx *c)
 {
 	const int L = c->cfg.L, K = c->cfg.K, A = c->Amax, KP = c->d.KP;
-	for (int k = 0; k < K; k++)
-		for (int j = 0; j < L; j++)
-			for (int a = 0; a < A; a++) c->freq_stage[((size_t)j * A + a) * KP + k] = c->freq[((size_t)k * L + j) * A + a];
+	freq_to_device(c->freq.data(), c->freq_stage.data(), K, L, A, KP);
 	HIPCHK(hipMemcpyAsync(c->d.freq, c->freq_stage.data(), sizeof(double) * (size_t)L * A * KP, hipMemcpyHostToDevice, c->stream));
 	return refresh_freqf(c);
 }
@@ -2369,9 +2273,7 @@ static int download_freq(isg_ctx *c)
 	const int L = c->cfg.L, K = c->cfg.K, A = c->Amax, KP = c->d.KP;
 	HIPCHK(hipMemcpyAsync(c->freq_stage.data(), c->d.freq, sizeof(double) * (size_t)L * A * KP, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	for (int k = 0; k < K; k++)
-		for (int j = 0; j < L; j++)
-			for (int a = 0; a < A; a++) c->freq[((size_t)k * L + j) * A + a] = c->freq_stage[((size_t)j * A + a) * KP + k];
+	freq_from_device(c->freq_stage.data(), c->freq.data(), K, L, A, KP);
 	return 0;
 }
 /* host mirrors are refreshed on demand only (getters, the host-side steps of the replay schedule) */
@@ -2456,12 +2358,9 @@ extern "C" int isg_count_alleles(isg_ctx *c, int32_t *counts)
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (c->poly) return poly_count_alleles(c, counts);
 	if (launch_count(c)) return 1;
-	const int L = c->cfg.L, K = c->cfg.K, A = c->Amax;
 	HIPCHK(hipMemcpyAsync(c->cnt_h.data(), c->d.cnt, sizeof(int) * c->cnt_h.size(), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	for (int k = 0; k < K; k++)
-		for (int j = 0; j < L; j++)
-			for (int a = 0; a < A; a++) counts[((size_t)k * L + j) * A + a] = c->cnt_h[((size_t)j * A + a) * K + k];
+	counts_from_device(c->cnt_h.data(), nullptr, counts, c->cfg.K, c->cfg.L, c->Amax);
 	return 0;
 }
 
@@ -2474,20 +2373,8 @@ static int update_P_ahead(isg_ctx *c)
 	c->ahead_valid = false;
 	if (c->poly || is_keyed(c) || !c->host_tape) return 0;
 	if (c->pdev && c->pdev->usable) return 0; /* update_P runs on the device: nothing for the host to get ahead with */
-	const int L = c->cfg.L, K = c->cfg.K;
 	if (launch_count(c)) return 1;
-	HIPCHK(hipMemcpyAsync(c->cnt_h.data(), c->d.cnt, sizeof(int) * c->cnt_h.size(), hipMemcpyDeviceToHost, c->stream));
-	if (counts_mark(c)) return 1;
-	uint64_t ngamma = 0;
-	for (int j = 0; j < L; j++) ngamma += (c->allelenum[j] > 1) ? (uint64_t)c->allelenum[j] * K : 0;
-	isg_cursor cur;
-	if (host_tape_begin(c, ngamma, &cur)) return 1;
-	if (!c->ev_tape) HIPCHK(hipEventCreateWithFlags(&c->ev_tape.e, hipEventDisableTiming));
-	HIPCHK(hipEventRecord(c->ev_tape, c->stream));
-	c->ahead_rng = c->rng;
-	c->ahead_ngamma = ngamma;
-	c->ahead_valid = true;
-	return 0;
+	return host_update_P(c, HOSTP_REQUEST, c->d.cnt, nullptr, true);
 }
 
 /* ---- update_P ---- */
@@ -2496,7 +2383,7 @@ extern "C" int isg_update_P(isg_ctx *c)
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (c->poly) return poly_update_P(c);
 	DevView &d = c->d;
-	const int L = c->cfg.L, K = c->cfg.K, A = c->Amax;
+	const int L = c->cfg.L, K = c->cfg.K;
 	/* requested at the end of the previous iteration's update_alpha (update_P_ahead), for exactly this stream position? */
 	const bool ahead = c->ahead_valid && !is_keyed(c) && c->ahead_rng.s1 == c->rng.s1 && c->ahead_rng.s2 == c->rng.s2 && c->ahead_rng.s3 == c->rng.s3;
 	c->ahead_valid = false;
@@ -2517,54 +2404,8 @@ extern "C" int isg_update_P(isg_ctx *c)
 		if (pdev_update_P(c, c->pdev, &done)) return 1;
 		if (done) return refresh_freqf(c);
 	}
+	if (host_update_P(c, ahead ? HOSTP_DRAW : HOSTP_REQUEST | HOSTP_DRAW, d.cnt, nullptr, true)) return 1;
 	auto ht0 = std::chrono::steady_clock::now();
-	isg_cursor cur;
-	uint64_t ngamma = 0;
-	if (ahead) {
-		ngamma = c->ahead_ngamma;
-		cur.s = c->rng;
-		cur.used = 0;
-		cur.tape = nullptr;
-	} else {
-		HIPCHK(hipMemcpyAsync(c->cnt_h.data(), d.cnt, sizeof(int) * c->cnt_h.size(), hipMemcpyDeviceToHost, c->stream));
-		if (counts_mark(c)) return 1;
-		for (int j = 0; j < L; j++) ngamma += (c->allelenum[j] > 1) ? (uint64_t)c->allelenum[j] * K : 0;
-		if (host_tape_begin(c, ngamma, &cur)) return 1;
-	}
-	if (counts_wait(c)) return 1;
-	HOST_T(c, 0, ht0); /* launches + wait for the counts */
-	/* the shapes (count + 1.0, rdirich's `add`) of all gammas in stream order and their constants, then the draws */
-	c->pshape.resize(ngamma);
-	c->pcoef.resize(ngamma);
-	{
-		size_t g = 0;
-		for (int k = 0; k < K; k++)
-			for (int j = 0; j < L; j++) {
-				const int Aj = c->allelenum[j];
-				if (Aj <= 1) continue;
-				for (int a = 0; a < Aj; a++) c->pshape[g++] = (double)c->cnt_h[((size_t)j * A + a) * K + k] + 1.0;
-			}
-	}
-	HOST_T(c, 1, ht0); /* shapes */
-	host_gamma_coefs(c->pshape.data(), (size_t)ngamma, (HostGammaCoef *)c->pcoef.data());
-	HOST_T(c, 2, ht0); /* constants */
-	if (ahead) HIPCHK(hipEventSynchronize(c->ev_tape)); /* (not the stream: the previous iteration's cal_lkh may still be running) */
-	else HIPCHK(hipStreamSynchronize(c->stream)); /* the tape */
-	HOST_T(c, 3, ht0); /* wait for the tape */
-	host_tape_attach(c, &cur);
-	{
-		size_t g = 0;
-		for (int k = 0; k < K; k++)
-			for (int j = 0; j < L; j++) {
-				const int Aj = c->allelenum[j];
-				if (Aj <= 1) continue;
-				host_tape_guard(c, &cur, Aj);
-				host_rdirich_pre(&cur, &c->pshape[g], (const HostGammaCoef *)c->pcoef.data() + g, Aj, &c->freq[((size_t)k * L + j) * A]);
-				g += (size_t)Aj;
-			}
-	}
-	host_tape_end(c, &cur);
-	HOST_T(c, 4, ht0); /* the sequential draws */
 	const int rc_up = upload_freq(c);
 	HOST_T(c, 5, ht0); /* transposition + upload launch */
 	c->host_n++;
@@ -3017,12 +2858,7 @@ extern "C" int isg_get_z(isg_ctx *c, int32_t *z)
 	std::vector<uint8_t> h((size_t)N * Lp * 2);
 	HIPCHK(hipMemcpyAsync(h.data(), c->d.z, h.size(), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	for (int i = 0; i < N; i++)
-		for (int j = 0; j < L; j++)
-			for (int k = 0; k < 2; k++) {
-				uint8_t v = h[((size_t)i * Lp + j) * 2 + k];
-				z[((size_t)i * L + j) * 2 + k] = (v == 0xff) ? -1 : (int)v;
-			}
+	bytes_to_ints(h.data(), z, N, L, Lp, 2);
 	return 0;
 }
 extern "C" int isg_set_z(isg_ctx *c, const int32_t *z)
@@ -3175,9 +3011,7 @@ extern "C" int isg_get_poly_freq2(isg_ctx *c, double *f) /* [K][L][Amax]: the se
 		HIPCHK(hipSetDevice(c->cfg.device));
 		HIPCHK(hipMemcpyAsync(c->freq_stage.data(), c->poly->p.freq2, sizeof(double) * (size_t)L * A * KP, hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
-		for (int k = 0; k < K; k++)
-			for (int j = 0; j < L; j++)
-				for (int a = 0; a < A; a++) c->poly->freq2_h[((size_t)k * L + j) * A + a] = c->freq_stage[((size_t)j * A + a) * KP + k];
+		freq_from_device(c->freq_stage.data(), c->poly->freq2_h.data(), K, L, A, KP);
 	}
 	memcpy(f, c->poly->freq2_h.data(), sizeof(double) * c->poly->freq2_h.size());
 	return 0;
@@ -3300,9 +3134,7 @@ extern "C" int isg_store_fetch(isg_ctx *c, double *qq, double *qq2, double *indv
 		const int L = c->cfg.L, A = c->Amax, KP = c->d.KP;
 		HIPCHK(hipMemcpyAsync(c->freq_stage.data(), which ? c->st_freq2 : c->st_freq, sizeof(double) * (size_t)L * A * KP, hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
-		for (int k = 0; k < (int)K; k++)
-			for (int j = 0; j < L; j++)
-				for (int a = 0; a < A; a++) dst[((size_t)k * L + j) * A + a] = c->freq_stage[((size_t)j * A + a) * KP + k];
+		freq_from_device(c->freq_stage.data(), dst, (int)K, L, A, KP);
 	}
 	if (steps) *steps = c->st_step;
 	return 0;

@@ -1746,6 +1746,19 @@ static void poly_launch_genfreq(isg_ctx *c, const float *self, int own)
 	do { if (p.allo) hipLaunchKernelGGL(k4_genfreq<true>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own); else hipLaunchKernelGGL(k4_genfreq<false>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own); } while (0);
 }
 
+/* What follows a draw of the frequencies, wherever it was made: the single precision rows for the Z pre-filter, then calc_exfreq_auto / _allo
+ * (it follows update_P_auto in the chain loop, poly_geno.c:102-103).  on_host: the host mirrors c->freq (and freq2_h) are what the device holds. */
+static int poly_after_draw(isg_ctx *c, bool on_host)
+{
+	if (refresh_freqf(c)) return 1;
+	prof_begin(c);
+	poly_launch_exfreq(c);
+	prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
+	HIPCHK(hipGetLastError());
+	c->poly->freq_host = on_host;
+	return 0;
+}
+
 static int poly_update_P(isg_ctx *c) /* update_P_auto */
 {
 	PolyDev &p = c->poly->p;
@@ -1756,87 +1769,28 @@ static int poly_update_P(isg_ctx *c) /* update_P_auto */
 		hipLaunchKernelGGL(k4_pdirich, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p, c->origin, iter_base(c), c->ky[KY_SP]);
 		prof_end(c, "k4_pdirich");
 		HIPCHK(hipGetLastError());
-		if (refresh_freqf(c)) return 1;
-		prof_begin(c);
-		poly_launch_exfreq(c);
-		prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
-		HIPCHK(hipGetLastError());
-		c->poly->freq_host = false;
-		return 0;
+		return poly_after_draw(c, false);
 	}
 	if (c->pdev && c->pdev->usable) { /* the Dirichlets' start positions resolved on the device, all of them drawn at once (isg_walk_hip.inc) */
 		bool done = false;
 		if (pdev_update_P(c, c->pdev, &done)) return 1;
-		if (done) {
-			if (refresh_freqf(c)) return 1;
-			prof_begin(c);
-			poly_launch_exfreq(c);
-			prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
-			HIPCHK(hipGetLastError());
-			c->poly->freq_host = false;
-			return 0;
-		}
+		if (done) return poly_after_draw(c, false);
 	}
-	HIPCHK(hipMemcpyAsync(c->cnt_h.data(), p.cnt, sizeof(int) * c->cnt_h.size(), hipMemcpyDeviceToHost, c->stream));
-	if (p.allo) HIPCHK(hipMemcpyAsync(c->poly->cnt2_h.data(), p.cnt2, sizeof(int) * c->poly->cnt2_h.size(), hipMemcpyDeviceToHost, c->stream));
-	if (counts_mark(c)) return 1;
-	isg_cursor cur;
-	uint64_t ngamma = 0;
-	for (int j = 0; j < L; j++) ngamma += (uint64_t)c->allelenum[j] * K * (p.allo ? 2 : 1);
-	if (host_tape_begin(c, ngamma, &cur)) return 1; /* the loop's uniforms, generated on the device */
-	if (counts_wait(c)) return 1;
-	/* the shapes (count + 1.0) of all gammas in stream order -- allotetraploid: per (cluster, locus) the first subgenome's, then
-	 * the second's (poly_geno.c:499-506) -- and rgamma2's shape-only constants, then the draws */
-	c->pshape.resize(ngamma);
-	c->pcoef.resize(ngamma);
-	{
-		size_t g = 0;
-		for (int k = 0; k < K; k++)
-			for (int j = 0; j < L; j++) { /* no allelenum > 1 test on this path (poly_geno.c:426-434) */
-				const int Aj = c->allelenum[j];
-				for (int a = 0; a < Aj; a++) c->pshape[g++] = (double)c->cnt_h[((size_t)j * A + a) * K + k] + 1.0;
-				if (p.allo)
-					for (int a = 0; a < Aj; a++) c->pshape[g++] = (double)c->poly->cnt2_h[((size_t)j * A + a) * K + k] + 1.0;
-			}
-	}
-	host_gamma_coefs(c->pshape.data(), (size_t)ngamma, (HostGammaCoef *)c->pcoef.data());
-	HIPCHK(hipStreamSynchronize(c->stream)); /* the tape */
-	host_tape_attach(c, &cur);
-	{
-		size_t g = 0;
-		const HostGammaCoef *coef = (const HostGammaCoef *)c->pcoef.data();
-		for (int k = 0; k < K; k++)
-			for (int j = 0; j < L; j++) {
-				const int Aj = c->allelenum[j];
-				host_tape_guard(c, &cur, Aj);
-				host_rdirich_pre(&cur, &c->pshape[g], coef + g, Aj, &c->freq[((size_t)k * L + j) * A]);
-				g += (size_t)Aj;
-				if (p.allo) {
-					host_tape_guard(c, &cur, Aj);
-					host_rdirich_pre(&cur, &c->pshape[g], coef + g, Aj, &c->poly->freq2_h[((size_t)k * L + j) * A]);
-					g += (size_t)Aj;
-				}
-			}
-	}
-	host_tape_end(c, &cur);
+	/* the host loop; no allelenum > 1 test on this path (poly_geno.c:426-434) */
+	const HostPSecond second = {p.cnt2, c->poly->cnt2_h.data(), c->poly->freq2_h.data()};
+	if (host_update_P(c, HOSTP_REQUEST | HOSTP_DRAW, p.cnt, p.allo ? &second : nullptr, false)) return 1;
+	auto ht0 = std::chrono::steady_clock::now();
 	if (p.allo) {
-		for (int k = 0; k < K; k++)
-			for (int j = 0; j < L; j++)
-				for (int a = 0; a < A; a++) c->freq_stage[((size_t)j * A + a) * p.KP + k] = c->poly->freq2_h[((size_t)k * L + j) * A + a];
+		freq_to_device(c->poly->freq2_h.data(), c->freq_stage.data(), K, L, A, p.KP);
 		HIPCHK(hipMemcpyAsync(p.freq2, c->freq_stage.data(), sizeof(double) * (size_t)L * A * p.KP, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream)); /* the staging buffer is reused for freq right below */
 	}
-	for (int k = 0; k < K; k++)
-		for (int j = 0; j < L; j++)
-			for (int a = 0; a < A; a++) c->freq_stage[((size_t)j * A + a) * p.KP + k] = c->freq[((size_t)k * L + j) * A + a];
+	freq_to_device(c->freq.data(), c->freq_stage.data(), K, L, A, p.KP);
 	HIPCHK(hipMemcpyAsync(p.freq, c->freq_stage.data(), sizeof(double) * (size_t)L * A * p.KP, hipMemcpyHostToDevice, c->stream));
-	if (refresh_freqf(c)) return 1; /* single precision rows for the Z pre-filter */
-	/* calc_exfreq_auto follows update_P_auto in the chain loop (poly_geno.c:102-103) */
-	prof_begin(c);
-	poly_launch_exfreq(c);
-	prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
-	HIPCHK(hipGetLastError());
-	return 0;
+	const int rc = poly_after_draw(c, true);
+	HOST_T(c, 5, ht0); /* transpositions + upload launches */
+	c->host_n++;
+	return rc;
 }
 
 static int poly_read_acc(isg_ctx *c, int nslots, std::vector<isg_acc> &out)
@@ -2127,10 +2081,7 @@ static int poly_count_alleles(isg_ctx *c, int32_t *counts)
 	HIPCHK(hipMemcpyAsync(c->cnt_h.data(), p.cnt, sizeof(int) * c->cnt_h.size(), hipMemcpyDeviceToHost, c->stream));
 	if (p.allo) HIPCHK(hipMemcpyAsync(c->poly->cnt2_h.data(), p.cnt2, sizeof(int) * c->poly->cnt2_h.size(), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	for (int k = 0; k < K; k++)
-		for (int j = 0; j < L; j++)
-			for (int a = 0; a < A; a++) /* allotetraploid: both subgenomes' copies (seqpop + seqpop2) */
-				counts[((size_t)k * L + j) * A + a] = c->cnt_h[((size_t)j * A + a) * K + k] + (p.allo ? c->poly->cnt2_h[((size_t)j * A + a) * K + k] : 0);
+	counts_from_device(c->cnt_h.data(), p.allo ? c->poly->cnt2_h.data() : nullptr, counts, K, L, A); /* allotetraploid: both subgenomes' copies (seqpop + seqpop2) */
 	return 0;
 }
 
@@ -2141,12 +2092,7 @@ static int poly_get_bytes(isg_ctx *c, const uint8_t *dev, int32_t *out)
 	std::vector<uint8_t> h((size_t)p.N * p.Lp * 4);
 	HIPCHK(hipMemcpyAsync(h.data(), dev, h.size(), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	for (int i = 0; i < p.N; i++)
-		for (int j = 0; j < p.L; j++)
-			for (int k = 0; k < 4; k++) {
-				const uint8_t v = h[((size_t)i * p.Lp + j) * 4 + k];
-				out[((size_t)i * p.L + j) * 4 + k] = (v == 0xff) ? -1 : (int)v;
-			}
+	bytes_to_ints(h.data(), out, p.N, p.L, p.Lp, 4);
 	return 0;
 }
 

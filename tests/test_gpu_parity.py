@@ -232,7 +232,8 @@ _P0 = dict(_S0, INSTRUCT_ZQ_RESOLVE_PERSIST="0")   # one launch per block instea
                                  _R0, dict(_R0, INSTRUCT_ZQ_PIPE="0"),
                                  dict(_R0, INSTRUCT_ZQ_PIPE_XCD="0"), dict(_R0, INSTRUCT_ZQ_SPEC="0"), dict(_R0, INSTRUCT_ZQ_XCD="1"),
                                  dict(_R0, INSTRUCT_ZQ_SPEC="0", INSTRUCT_ZQ_XCD="1"), dict(_R0, INSTRUCT_ZQ_COOP="0"),
-                                 {"INSTRUCT_P_DEVICE": "0"}, {"INSTRUCT_LL_INT": "0"}, {"INSTRUCT_LL_TABLES": "0"}])   # (likelihood terms: double tables / evaluated directly)
+                                 {"INSTRUCT_P_DEVICE": "0"}, {"INSTRUCT_LL_INT": "0"}, {"INSTRUCT_LL_TABLES": "0"},   # (likelihood terms: double tables / evaluated directly)
+                                 {"INSTRUCT_P_DEVICE": "0", "INSTRUCT_HOST_TAPE": "0"}])   # (update_P's host loop stepping the generator itself)
 @pytest.mark.parametrize("case", [(24, 700, 5, 0.05, 2), (6, 40000, 3, 0.02, 2), (8, 33000, 9, 0.0, 3),
                                   (10, 20000, 8, 0.03, 3), (16, 3000, 2, 0.1, 2)])
 def test_replay_zq_kernel_variants_bit_exact_vs_canonical_oracle(case, env, monkeypatch):
@@ -248,6 +249,32 @@ def test_replay_zq_kernel_variants_bit_exact_vs_canonical_oracle(case, env, monk
     o.chain_init(initd)
     _same(h, o, ["z", "qq", "qqnum", "seeds"], "init")
     for it in range(2):
+        h.iteration()
+        o.iteration()
+        _same(h, o, ["z", "qq", "qqnum", "generation", "alpha", "self_rates", "freq", "indvlkh", "totallkh", "seeds"], it)
+    h.close()
+
+
+def test_replay_host_update_P_requested_ahead_bit_exact_vs_canonical_oracle(monkeypatch):
+    """INSTRUCT_P_DEVICE=0, three iterations: from the second update_P on, the counts and the uniform tape (K x 2985 two-allele loci x 2 = 11940 gammas, above
+    the 4096 from which there is one) were requested at the end of the previous iteration's update_alpha, ahead of cal_lkh.
+    A column overwritten with one allele BEFORE coding does not reach the sampler: code_diploid drops monomorphic loci as the reference's
+    transform_data does.  So the column is overwritten (and seen to be dropped), and one locus of the coded data is made single-allele
+    instead -- allelenum 1, every copy 0 -- which update_P passes over without drawing (its allelenum > 1 test)."""
+    monkeypatch.setenv("INSTRUCT_P_DEVICE", "0")
+    N, L, K = 16, 3001, 2
+    raw = synth.raw_alleles(N, L, K, 2, 2, 0.1, 29)
+    full = synth.code_diploid(raw)[1].size
+    raw[:, 7, :] = np.where(raw[:, 7, :] == synth.MISSING, synth.MISSING, 1)
+    geno, an, mi = synth.code_diploid(raw)
+    assert an.size == full - 1 and an.min() == 2
+    geno[:, 11, :] = np.where(geno[:, 11, :] == synth.MISSING, synth.MISSING, 0)
+    an[11] = 1
+    h, o, initd = _pair(geno, an, mi, K, capi.SCHED_REPLAY)
+    h.chain_init(initd)
+    o.chain_init(initd)
+    _same(h, o, ["z", "qq", "qqnum", "seeds"], "init")
+    for it in range(3):
         h.iteration()
         o.iteration()
         _same(h, o, ["z", "qq", "qqnum", "generation", "alpha", "self_rates", "freq", "indvlkh", "totallkh", "seeds"], it)

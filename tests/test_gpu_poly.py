@@ -286,6 +286,40 @@ def test_tetraploid_matches_reference_golden(name):
             assert x == y or (x != x and y != y) or abs(x - y) <= 1e-9 * max(abs(x), abs(y)), (g, w)
 
 
+# ---------------------------------------------------------------------------------------------- replay update_P's host loop
+@pytest.mark.parametrize("name,env", [("t1", {"INSTRUCT_P_DEVICE": "0"}), ("x_a4k3", {"INSTRUCT_P_DEVICE": "0"}), ("xa_a3k9", {"INSTRUCT_HOST_TAPE": "0"})])
+def test_tetraploid_host_update_P_bit_identical_to_canonical_oracle(name, env, tmp_path, monkeypatch):
+    """The sequential host loop of replay update_P (isg_host_dirichlet.h) for ploidy 4, where no allelenum > 1 test applies.  Autotetraploid
+    chains only reach it with INSTRUCT_P_DEVICE=0; allotetraploid ones always do, here with the generator stepped on the host
+    (INSTRUCT_HOST_TAPE=0).  Gammas per sweep, K x sum of the loci's alleles x subgenomes: t1 at most 3 x 40 x 4 = 480, below the 4096 from which
+    the uniforms come from the device; x_a4k3 at most 3 x 1500 x 4 = 18000, tape in use; xa_a3k9 at most 9 x 700 x 3 x 2 = 37800, where the
+    tape would be in use and is switched off.  Two or three iterations, every dump line equal to the canonical oracle's."""
+    from instruct_amd import synth
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    allo = name.startswith("xa_")
+    if name in POLY:   # the golden case's data and seeds, three iterations of it
+        cfg = POLY[name][:5] + (3, 1, 1, POLY[name][8], 1, 1, POLY[name][11])
+        raw = gu.make_golden.poly_data_for(name)
+    elif allo:
+        cfg = ALLO_EXTRA[name]
+        raw = synth.raw_alleles(cfg[0], cfg[1], cfg[2], 4, cfg[3], cfg[4], 20260401 + sorted(ALLO_EXTRA).index(name))
+    else:
+        cfg, raw = EXTRA[name], extra_data(name)
+    N, L, K, A, miss, u, b, t, e, r, j, seeds = cfg
+    txt, out = str(tmp_path / (name + ".txt")), str(tmp_path / (name + ".can"))
+    synth.write_text_polyploid(txt, raw)
+    if allo:
+        want = _allo_oracle(txt, out, cfg, True)
+    else:
+        assert subprocess.call([DUMP, txt, out] + [str(x) for x in (K, N, L, u, b, t, e, r, j) + tuple(seeds)] + ["1", "1"]) == 0
+        want = [l for l in gu.parse(out) if l.startswith("it ") or l.startswith("chain zqinit")]
+    got = hip_lines(name, cfg, raw, allo=allo)
+    assert len(got) == len(want) == 1 + 6 * u and u in (2, 3)
+    for g, w in zip(got, want):
+        assert _norm(g) == _norm(w)
+
+
 # ---------------------------------------------------------------------------------------------- BASELINE config 5
 C5 = dict(N=10000, L=20000, K=10, A=4, miss=0.05)
 
