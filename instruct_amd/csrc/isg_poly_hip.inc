@@ -545,57 +545,12 @@ __global__ void k4_genfreq(PolyDev p, const float *self, int own)
 }
 
 /*
- * Wide-allele contexts (more than 16 alleles at some locus, up to 32): the table kernels above run ONE lane per (cluster, locus) and find every
- * row by linear search (isg_poly_find, O(G) per term), which no longer scales.  Here a workgroup takes one (cluster, locus) table.
- *   k4_exfreq_w   lanes over the genotypes, the table's allele frequencies staged in LDS; each entry is exfreq_row's / exfreq_row_allo's
- *                 expression for that row (same float / double pattern, same bits)
- *   k4_genfreq_w  the classes in dependency order with a workgroup barrier between them -- autotetraploid: quadri -> tri triples (3x3 solve
- *                 per triple) -> duplex -> simplex -> mono; allotetraploid: ijkl -> ijkk and iikl -> iikk.  Within a class every row depends
- *                 only on rows of earlier classes, so a lane forms its row's sum term by term in genfreq_row's order (the `sic` reuse and the
- *                 n >= 3 / n >= 4 branches included) and the row comes out as genfreq_row computes it; rows are found in closed form
- *                 (isg_poly_rank, isg_allo_row_any).
+ * Wide-allele contexts (more than 16 alleles at some locus, up to 32): one lane per table no longer scales, so here a workgroup takes one
+ * (cluster, locus) table and its lanes share the rows.  The rows themselves are the per-row functions of isg_poly_tables.h, the ones the
+ * kernels above run serially.  k4_genfreq_w takes the classes in dependency order -- autotetraploid: quadri -> tri (one lane per triple)
+ * -> duplex -> simplex -> mono; allotetraploid: ijkl -> iikl and ijkk -> iikk.  A row reads only rows of earlier classes, so a workgroup
+ * barrier between two classes is all the ordering it needs.
  */
-__device__ __forceinline__ float exfreq_auto_at(const isg_polyclass &pc, const double *f, int r)
-{
-	const int n = pc.n, P = 4;
-	int tmp = pc.list[r], digit[4];
-	int b = pc.g[1];
-	if (r < b) return (float)isg_log(f[tmp % n]) * (float)P;
-	if (r < (b += pc.g[2])) {
-		digit[0] = tmp % n;
-		tmp /= n;
-		digit[1] = tmp % n;
-		return (float)(isg_log(4.0) + isg_log(f[digit[1]]) * (float)(P - 1) + isg_log(f[digit[0]]));
-	}
-	if (r < (b += pc.g[3])) {
-		digit[0] = tmp % n;
-		tmp /= (n * n);
-		digit[1] = tmp % n;
-		return (float)(isg_log(6.0) + (isg_log(f[digit[1]]) + isg_log(f[digit[0]])) * (P / 2));
-	}
-	if (r < (b += pc.g[4])) {
-		for (int m = 0; m < P - 1; m++) { digit[m] = tmp % n; tmp /= n; }
-		return (float)(isg_log(12.0) + isg_log(f[digit[2]]) * (P / 2) + isg_log(f[digit[0]]) + isg_log(f[digit[1]]));
-	}
-	for (int m = 0; m < P; m++) { digit[m] = tmp % n; tmp /= n; }
-	float ex = (float)isg_log(24.0);
-	for (int m = 0; m < P; m++) ex += (float)isg_log(f[digit[m]]);
-	return ex;
-}
-__device__ __forceinline__ float exfreq_allo_at(const isg_polyclass &pc, const double *f, const double *f2, int r)
-{
-	const int n = pc.n, code = pc.list[r], d0 = code % n, d1 = (code / n) % n, d2 = (code / n / n) % n, d3 = code / n / n / n;
-	if (r < pc.g[1]) return (float)((isg_log(f[d2]) + isg_log(f2[d0])) * 2);
-	if (r < pc.g[1] + pc.g[2]) return (float)(isg_log(2.0) + isg_log(f[d2]) * 2 + isg_log(f2[d0]) + isg_log(f2[d1]));
-	if (r < pc.g[1] + pc.g[2] + pc.g[3]) return (float)(isg_log(2.0) + isg_log(f2[d1]) * 2 + isg_log(f[d3]) + isg_log(f[d2]));
-	float ex = (float)isg_log(4.0);
-	ex += (float)isg_log(f2[d0]);
-	ex += (float)isg_log(f2[d1]);
-	ex += (float)isg_log(f[d2]);
-	ex += (float)isg_log(f[d3]);
-	return ex;
-}
-
 /* calc_exfreq_auto / calc_exfreq_allo: one workgroup per (cluster, locus) table, blockIdx.x = k L + j */
 template <bool ALLO>
 __global__ void __launch_bounds__(256) k4_exfreq_w(PolyDev p)
@@ -609,7 +564,7 @@ __global__ void __launch_bounds__(256) k4_exfreq_w(PolyDev p)
 	}
 	__syncthreads();
 	float *ex = p.exfreq + (size_t)id * p.GS;
-	for (int r = t; r < pc.G; r += 256) ex[r] = ALLO ? exfreq_allo_at(pc, fs[0], fs[1], r) : exfreq_auto_at(pc, fs[0], r);
+	for (int r = t; r < pc.G; r += 256) ex[r] = ALLO ? ptd_exfreq_allo_at(&pc, fs[0], fs[1], r) : ptd_exfreq_at(&pc, fs[0], r);
 }
 
 /* auto_genfreq / allo_genfreq at the selfing rates self[k] into genofreq (own) or tabtmp: one workgroup per table, blockIdx.x = k L + j */
@@ -618,130 +573,27 @@ __global__ void __launch_bounds__(256) k4_genfreq_w(PolyDev p, const float *self
 {
 	const int id = (int)blockIdx.x, k = id / p.L, j = id - k * p.L, t = (int)threadIdx.x;
 	const isg_polyclass pc = p.pc[p.lclass[j]];
-	const int n = pc.n, G = pc.G, b1 = pc.g[1], b2 = b1 + pc.g[2], b3 = b2 + pc.g[3], b4 = b3 + pc.g[4];
+	const int G = pc.G, b1 = pc.g[1], b2 = b1 + pc.g[2], b3 = b2 + pc.g[3], b4 = b3 + pc.g[4];
 	const float s = self[k];
 	const float *ex = p.exfreq + (size_t)id * p.GS;
 	float *fr = (own ? p.genofreq : p.tabtmp) + (size_t)id * p.GS;
 	int e = 0;
 	if (ALLO) {
-		for (int r = b3 + t; r < G; r += 256) { /* ijkl */
-			fr[r] = (float)(isg_log((double)(1 - s)) + ex[r] - isg_log((double)(1 - s / 4)));
-			if (fr[r] > 0) e |= 4;
-		}
+		for (int r = b3 + t; r < G; r += 256) ptd_genfreq_allo_ijkl_at(s, ex, fr, r, &e);
 		__syncthreads();
-		for (int r = b1 + t; r < b3; r += 256) { /* iikl and ijkk: both from ijkl rows only */
-			const int code = pc.list[r];
-			float temp = 0;
-			if (r >= b2) { /* ijkk */
-				const int kk = code % n, b = (code / n / n) % n, a = code / n / n / n;
-				for (int v = 0; v < n; v++)
-					if (v != kk) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, b, kk, v)]) * s / 8.0);
-			} else { /* iikl */
-				const int d = code % n, c = (code / n) % n, a = (code / n / n) % n;
-				for (int v = 0; v < n; v++)
-					if (v != a) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, v, c, d)]) * s / 8.0);
-			}
-			fr[r] = (float)(isg_log((1 - s) * isg_exp((double)ex[r]) + temp) - isg_log(1 - s / 2.0));
-			if (fr[r] > 0) e |= 4;
-		}
+		for (int r = b1 + t; r < b3; r += 256) ptd_genfreq_allo_het_at(s, &pc, ex, fr, r, &e);
 		__syncthreads();
-		for (int r = t; r < b1; r += 256) { /* iikk */
-			const int code = pc.list[r], kk = code % n, a = (code / n / n) % n;
-			float temp = 0;
-			for (int v = 0; v < n; v++)
-				if (v != kk) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, a, kk, v)]) * s / 4.0);
-			for (int v = 0; v < n; v++)
-				if (v != a) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, v, kk, kk)]) * s / 4.0);
-			for (int v = 0; v < n; v++)
-				for (int w = 0; w < n; w++)
-					if (v != a && w != kk) temp = (float)(temp + isg_exp((double)fr[isg_allo_row_any(n, a, v, kk, w)]) * s / 16.0);
-			fr[r] = (float)(isg_log((1 - s) * isg_exp((double)ex[r]) + temp) - isg_log((double)(1 - s)));
-			if (fr[r] > 0) e |= 4;
-		}
+		for (int r = t; r < b1; r += 256) ptd_genfreq_allo_iikk_at(s, &pc, ex, fr, r, &e);
 	} else {
-		if (n >= 4)
-			for (int i = b4 + t; i < G; i += 256) { /* quadri ijkl */
-				fr[i] = (float)(isg_log((double)(1 - s)) + ex[i] - isg_log((double)(1 - s / 6)));
-				if (fr[i] > 0) e |= 4;
-			}
+		for (int r = b4 + t; r < G; r += 256) ptd_genfreq_quadri_at(s, ex, fr, r, &e);
 		__syncthreads();
-		if (n >= 3)
-			for (int q = t; q < pc.g[4] / 3; q += 256) { /* tri iijk: one lane per triple */
-				const int r0 = b3 + 3 * q;
-				int num = pc.list[r0], digit[3];
-				for (int m = 2; m >= 0; m--) { digit[m] = num % n; num /= n; }
-				float temp = 0, matr[4][4], vec[4];
-				if (n >= 4) {
-					for (int l = 0; l < n; l++)
-						if (l != digit[0] && l != digit[1] && l != digit[2]) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, digit[0], digit[1], digit[2], l)]));
-					if (temp > 1) e |= 4;
-				}
-				for (int a = 1; a <= 3; a++) {
-					for (int b = 1; b <= 3; b++) {
-						if (a == b) matr[a][b] = (float)(1 - s * 10.0 / 36.0);
-						else matr[a][b] = (float)(-s / 9.0);
-					}
-					vec[a] = (float)(s / 18.0 * temp + (1.0 - s) * isg_exp((double)ex[r0 + a - 1]));
-				}
-				temp = vec[1];
-				for (int a = 1; a <= 3; a++) vec[a] /= temp;
-				isg_poly_gaussj3(matr, vec, &e);
-				for (int a = 0; a < 3; a++) {
-					fr[r0 + a] = (float)(isg_log((double)vec[a + 1]) + isg_log((double)temp));
-					if (fr[r0 + a] > 0) e |= 4;
-				}
-			}
+		for (int r = b3 + 3 * t; r < b4; r += 3 * 256) ptd_genfreq_tri_at(s, &pc, ex, fr, r, &e);
 		__syncthreads();
-		for (int i = b2 + t; i < b3; i += 256) { /* duplex iijj */
-			int num = pc.list[i];
-			const int d0 = num % n;
-			num /= (n * n);
-			const int d1 = num % n;
-			float temp = 0;
-			if (n >= 3)
-				for (int x = 0; x < n; x++)
-					if (x != d0 && x != d1) {
-						temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d1, d1, d0, x)]) / 9.0 * s);
-						temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d0, d0, d1, x)]) / 9.0 * s);
-						temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, x, x, d1, d0)]) / 36.0 * s);
-						if (n >= 4)
-							for (int y = x + 1; y < n; y++)
-								if (y != d0 && y != d1) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d0, d1, x, y)]) / 36.0 * s);
-					}
-			fr[i] = (float)(isg_log((1 - s) * isg_exp((double)ex[i]) + temp) - isg_log(1 - s / 2.0));
-			if (fr[i] > 0) e |= 4;
-		}
+		for (int r = b2 + t; r < b3; r += 256) ptd_genfreq_duplex_at(s, &pc, ex, fr, r, &e);
 		__syncthreads();
-		for (int i = b1 + t; i < b2; i += 256) { /* simplex iiij */
-			int num = pc.list[i];
-			const int d0 = num % n;
-			num /= n;
-			const int d1 = num % n;
-			float temp = (float)(8.0 / 36.0 * isg_exp((double)fr[isg_poly_rank(n, d0, d0, d1, d1)]) * s);
-			if (n >= 3)
-				for (int x = 0; x < n; x++)
-					if (x != d0 && x != d1) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, d1, d1, d0, x)]) / 9.0 * s);
-			fr[i] = (float)(isg_log((1 - s) * isg_exp((double)ex[i]) + temp) - isg_log(1 - s / 2.0));
-			if (fr[i] > 0) e |= 4;
-		}
+		for (int r = b1 + t; r < b2; r += 256) ptd_genfreq_simplex_at(s, &pc, ex, fr, r, &e);
 		__syncthreads();
-		for (int i = t; i < b1; i += 256) { /* mono iiii */
-			const int a = pc.list[i] % n;
-			float temp = 0;
-			for (int x = 0; x < n; x++)
-				if (x != a) {
-					int row = isg_poly_rank(n, a, a, a, x);
-					temp = (float)(temp + isg_exp((double)fr[row]) / 4.0 * s);
-					/* sic (as genfreq_row): for a > x the duplex term reuses the simplex row */
-					if (a < x) row = isg_poly_rank(n, a, a, x, x);
-					temp = (float)(temp + isg_exp((double)fr[row]) / 36.0 * s);
-					if (n >= 3)
-						for (int y = x + 1; y < n; y++)
-							if (y != a) temp = (float)(temp + isg_exp((double)fr[isg_poly_rank(n, a, a, x, y)]) / 36.0 * s);
-				}
-			fr[i] = (float)(isg_log((1 - s) * isg_exp((double)ex[i]) + temp) - isg_log((double)(1 - s)));
-			if (fr[i] > 0) e |= 4;
-		}
+		for (int r = t; r < b1; r += 256) ptd_genfreq_mono_at(s, &pc, ex, fr, r, &e);
 	}
 	if (e) atomicOr(p.err, 4u);
 }
@@ -1731,7 +1583,8 @@ static void poly_launch_exfreq(isg_ctx *c)
 		else hipLaunchKernelGGL(k4_exfreq_w<false>, dim3((unsigned)(K * L)), dim3(256), 0, c->stream, p);
 		return;
 	}
-	do { if (p.allo) hipLaunchKernelGGL(k4_exfreq<true>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); else hipLaunchKernelGGL(k4_exfreq<false>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p); } while (0);
+	if (p.allo) hipLaunchKernelGGL(k4_exfreq<true>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p);
+	else hipLaunchKernelGGL(k4_exfreq<false>, dim3((K * L + 127) / 128), dim3(128), 0, c->stream, p);
 }
 /* auto_genfreq / allo_genfreq for every table at the rates self[k]: into genofreq (own) or tabtmp */
 static void poly_launch_genfreq(isg_ctx *c, const float *self, int own)
@@ -1743,7 +1596,8 @@ static void poly_launch_genfreq(isg_ctx *c, const float *self, int own)
 		else hipLaunchKernelGGL(k4_genfreq_w<false>, dim3((unsigned)(K * L)), dim3(256), 0, c->stream, p, self, own);
 		return;
 	}
-	do { if (p.allo) hipLaunchKernelGGL(k4_genfreq<true>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own); else hipLaunchKernelGGL(k4_genfreq<false>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own); } while (0);
+	if (p.allo) hipLaunchKernelGGL(k4_genfreq<true>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own);
+	else hipLaunchKernelGGL(k4_genfreq<false>, dim3((K * L + 63) / 64), dim3(64), 0, c->stream, p, self, own);
 }
 
 /* What follows a draw of the frequencies, wherever it was made: the single precision rows for the Z pre-filter, then calc_exfreq_auto / _allo

@@ -76,8 +76,9 @@ static inline void isg_poly_build(int i, int g[6], int *list)
  * each < n).  With C(m, r) the binomial and rank_r(c_0 < .. < c_{r-1}) = C(n, r) - 1 - sum_i C(n - 1 - c_i, r - i) the rank of a
  * combination in lexicographic order:
  *   iiii  a | iiij  g1 + 2 rank_2(min, max) + (triple allele is the larger) | iijj  g1 + g2 + rank_2 | iijk  g1 + g2 + g3 + 3 rank_3(i, j, k)
- *   + (position of the doubled allele among the three) | ijkl  g1 + g2 + g3 + g4 + rank_4.  The wide-allele kernels use it instead of a
- * code -> row map (n^4 entries, rows beyond a short above 16 alleles).
+ *   + (position of the doubled allele among the three) | ijkl  g1 + g2 + g3 + g4 + rank_4.  The table rows below find every row with it
+ * (the reference searches the list: find_id, poly_geno.c:2367-2381; same rows), and so do the sweeps above 16 alleles, where a
+ * code -> row map (n^4 entries, rows beyond a short) no longer fits.
  */
 ISG_HD int isg_poly_binom(int m, int r)
 {
@@ -111,34 +112,6 @@ ISG_HD int isg_poly_exists(int value, const int *vec, int leng) /* data_interfac
 	for (i = 0; i < leng; i++)
 		if (value == vec[i]) flag = 1;
 	return flag;
-}
-ISG_HD int isg_poly_find(int num, const int *array, int len, int *err) /* find_id, poly_geno.c:2367-2381 */
-{
-	int i;
-	for (i = 0; i < len; i++)
-		if (array[i] == num) return i;
-	*err |= 1;
-	return 0;
-}
-ISG_HD int isg_poly_calc_val(const int *num, int val, int i) /* poly_geno.c:2305-2330 */
-{
-	int temp = 0;
-	if (val < num[0]) temp = val * i * i * i + num[0] * i * i + num[1] * i + num[2];
-	else if (val > num[0] && val < num[1]) temp = num[0] * i * i * i + val * i * i + num[1] * i + num[2];
-	else if (val > num[1] && val < num[2]) temp = num[0] * i * i * i + num[1] * i * i + val * i + num[2];
-	else if (val > num[2]) temp = num[0] * i * i * i + num[1] * i * i + num[2] * i + val;
-	return temp;
-}
-ISG_HD int isg_poly_calc_val2(const int *num, int val1, int val2, int i) /* poly_geno.c:2332-2365 */
-{
-	int temp = 0;
-	if (val2 < num[1]) temp = val1 * i * i * i + val2 * i * i + num[1] * i + num[0];
-	else if (val2 > num[1] && val2 < num[0] && val1 < num[1]) temp = val1 * i * i * i + num[1] * i * i + val2 * i + num[0];
-	else if (val1 > num[1] && val2 < num[0]) temp = num[1] * i * i * i + val1 * i * i + val2 * i + num[0];
-	else if (val1 > num[1] && val1 < num[0] && val2 > num[0]) temp = num[1] * i * i * i + val1 * i * i + num[0] * i + val2;
-	else if (val1 > num[0]) temp = num[1] * i * i * i + num[0] * i * i + val1 * i + val2;
-	else if (val1 < num[1] && val2 > num[0]) temp = val1 * i * i * i + num[1] * i * i + i * num[0] + val2;
-	return temp;
 }
 /* gaussj (poly_geno.c:2384-2435) for the 3x3 system with one right-hand side, float, 1-based */
 ISG_HD void isg_poly_gaussj3(float a[4][4], float b[4], int *err)
@@ -242,224 +215,214 @@ static inline void isg_allo_build(int n, int g[6], int *list)
 }
 #endif /* ISG_POLY_COMMON */
 
-/* ---- instantiated part: needs PT_NAME, PT_LOG, PT_EXP ---- */
+/* ---- instantiated part: needs PT_NAME, PT_LOG, PT_EXP ----
+ *
+ * One function per table ROW; each expression of the tables is written here once.  A row function reads the code of its own row
+ * from pc->list, finds every other row in closed form (isg_poly_rank, isg_allo_row_any) and, for genfreq, reads only rows of fr
+ * that belong to classes solved BEFORE its own -- autotetraploid: quadri -> tri -> duplex -> simplex -> mono; allotetraploid:
+ * ijkl -> {iikl, ijkk} -> iikk.  So the rows of one class can be computed in any order or side by side, as long as the classes
+ * come in that order (tests/test_poly_tables.py checks exactly this on the CPU).  The whole-row functions further down are the
+ * serial schedule (the oracle, the one-lane-per-table kernels); the wide-allele kernels spread a class over a workgroup's lanes.
+ * *err |= 4 when a log frequency comes out positive (the reference aborts: "Genotype frequencies can not be greater than 1!"),
+ * |= 2 from the 3x3 solve.
+ */
 
-/* calc_exfreq_auto for one (cluster, locus): f = allele frequencies of the cluster at the locus */
-ISG_HD void PT_NAME(exfreq_row)(const isg_polyclass *pc, const double *f, float *ex)
+/* calc_exfreq_auto (poly_geno.c:1515-1590), row r: f = allele frequencies of the cluster at the locus */
+ISG_HD float PT_NAME(exfreq_at)(const isg_polyclass *pc, const double *f, int r)
 {
 	const int n = pc->n, P = 4;
-	int j, m, digit[4], temp, tmp;
-	for (j = 0; j < pc->g[1]; j++) {
-		tmp = pc->list[j];
-		digit[0] = tmp % n;
-		ex[j] = (float)PT_LOG(f[digit[0]]) * (float)P;
-	}
-	temp = pc->g[1];
-	for (j = temp; j < temp + pc->g[2]; j++) {
-		tmp = pc->list[j];
+	int tmp = pc->list[r], digit[4], m, b = pc->g[1];
+	float ex;
+	if (r < b) return (float)PT_LOG(f[tmp % n]) * (float)P;
+	if (r < (b += pc->g[2])) {
 		digit[0] = tmp % n;
 		tmp /= n;
 		digit[1] = tmp % n;
-		ex[j] = (float)(PT_LOG(4.0) + PT_LOG(f[digit[1]]) * (float)(P - 1) + PT_LOG(f[digit[0]]));
+		return (float)(PT_LOG(4.0) + PT_LOG(f[digit[1]]) * (float)(P - 1) + PT_LOG(f[digit[0]]));
 	}
-	temp += pc->g[2];
-	for (j = temp; j < temp + pc->g[3]; j++) {
-		tmp = pc->list[j];
+	if (r < (b += pc->g[3])) {
 		digit[0] = tmp % n;
 		tmp /= (n * n);
 		digit[1] = tmp % n;
-		ex[j] = (float)(PT_LOG(6.0) + (PT_LOG(f[digit[1]]) + PT_LOG(f[digit[0]])) * (P / 2));
+		return (float)(PT_LOG(6.0) + (PT_LOG(f[digit[1]]) + PT_LOG(f[digit[0]])) * (P / 2));
 	}
-	temp += pc->g[3];
-	for (j = temp; j < temp + pc->g[4]; j++) {
-		tmp = pc->list[j];
+	if (r < (b += pc->g[4])) {
 		for (m = 0; m < P - 1; m++) { digit[m] = tmp % n; tmp /= n; }
-		ex[j] = (float)(PT_LOG(12.0) + PT_LOG(f[digit[2]]) * (P / 2) + PT_LOG(f[digit[0]]) + PT_LOG(f[digit[1]]));
+		return (float)(PT_LOG(12.0) + PT_LOG(f[digit[2]]) * (P / 2) + PT_LOG(f[digit[0]]) + PT_LOG(f[digit[1]]));
 	}
-	temp += pc->g[4];
-	for (j = temp; j < temp + pc->g[5]; j++) {
-		tmp = pc->list[j];
-		for (m = 0; m < P; m++) { digit[m] = tmp % n; tmp /= n; }
-		ex[j] = (float)PT_LOG(24.0);
-		for (m = 0; m < P; m++) ex[j] += (float)PT_LOG(f[digit[m]]);
-	}
+	for (m = 0; m < P; m++) { digit[m] = tmp % n; tmp /= n; }
+	ex = (float)PT_LOG(24.0);
+	for (m = 0; m < P; m++) ex += (float)PT_LOG(f[digit[m]]);
+	return ex;
 }
 
-/* auto_genfreq for one (cluster, locus): ex = its exfreq row, fr = output row; *err |= 4 when a log
- * frequency comes out positive (the reference aborts: "Genotype frequencies can not be greater than 1!") */
-ISG_HD void PT_NAME(genfreq_row)(float self, const isg_polyclass *pc, const float *ex, float *fr, int *err)
+/* auto_genfreq (poly_geno.c:1803-2028) at selfing rate self, row by row: ex = the table's exfreq row, fr = its output row */
+ISG_HD void PT_NAME(genfreq_quadri_at)(float self, const float *ex, float *fr, int r, int *err) /* ijkl */
 {
-	const int n = pc->n, G = pc->G, tri = 3, P = 4;
-	const int *gl = pc->list;
-	int i, j, k, l, tmp, digit[3], num = 0;
-	float temp, matr[4][4], vec[4];
-	tmp = G;
-	if (n >= 4)
-		for (i = tmp - pc->g[5]; i < tmp; i++) {
-			fr[i] = (float)(PT_LOG((double)(1 - self)) + ex[i] - PT_LOG((double)(1 - self / 6)));
-			if (fr[i] > 0) *err |= 4;
+	fr[r] = (float)(PT_LOG((double)(1 - self)) + ex[r] - PT_LOG((double)(1 - self / 6)));
+	if (fr[r] > 0) *err |= 4;
+}
+/* iijk: the three rows r0, r0 + 1, r0 + 2 of one allele triple (each allele doubled in turn) come out of one 3x3 system */
+ISG_HD void PT_NAME(genfreq_tri_at)(float self, const isg_polyclass *pc, const float *ex, float *fr, int r0, int *err)
+{
+	const int n = pc->n, tri = 3;
+	int num = pc->list[r0], digit[3], j, k, l;
+	float temp = 0, matr[4][4], vec[4];
+	for (j = tri - 1; j >= 0; j--) { digit[j] = num % n; num /= n; }
+	if (n >= 4) {
+		for (l = 0; l < n; l++)
+			if (l != digit[0] && l != digit[1] && l != digit[2])
+				temp = (float)(temp + PT_EXP((double)fr[isg_poly_rank(n, digit[0], digit[1], digit[2], l)]));
+		if (temp > 1) *err |= 4;
+	}
+	for (j = 1; j <= tri; j++) {
+		for (k = 1; k <= tri; k++) {
+			if (j == k) matr[j][k] = (float)(1 - self * 10.0 / 36.0);
+			else matr[j][k] = (float)(-self / 9.0);
 		}
-	if (n >= 3) {
-		tmp -= pc->g[5];
-		for (i = 0; i < pc->g[4] / tri; i++) {
-			num = gl[tmp - pc->g[4] + i * 3];
-			for (j = P - 2; j >= 0; j--) { digit[j] = num % n; num /= n; }
-			temp = 0;
-			if (n >= 4) {
-				for (l = 0; l < n; l++)
-					if (isg_poly_exists(l, digit, tri) == 0) {
-						num = isg_poly_find(isg_poly_calc_val(digit, l, n), gl, G, err);
-						temp = (float)(temp + PT_EXP((double)fr[num]));
-					}
-				if (temp > 1) *err |= 4;
-			}
-			for (j = 1; j <= tri; j++) {
-				for (k = 1; k <= tri; k++) {
-					if (j == k) matr[j][k] = (float)(1 - self * 10.0 / 36.0);
-					else matr[j][k] = (float)(-self / 9.0);
-				}
-				vec[j] = (float)(self / 18.0 * temp + (1.0 - self) * PT_EXP((double)ex[tmp - pc->g[4] + i * 3 + j - 1]));
-			}
-			temp = vec[1];
-			for (j = 1; j <= tri; j++) vec[j] /= temp;
-			isg_poly_gaussj3(matr, vec, err);
-			for (j = 0; j < tri; j++) {
-				fr[tmp - pc->g[4] + i * 3 + j] = (float)(PT_LOG((double)vec[j + 1]) + PT_LOG((double)temp));
-				if (fr[tmp - pc->g[4] + i * 3 + j] > 0) *err |= 4;
-			}
-		}
+		vec[j] = (float)(self / 18.0 * temp + (1.0 - self) * PT_EXP((double)ex[r0 + j - 1]));
 	}
-	tmp -= pc->g[4];
-	for (i = tmp - pc->g[3]; i < tmp; i++) { /* duplex iijj */
-		num = gl[i];
-		digit[0] = num % n;
-		num /= (n * n);
-		digit[1] = num % n;
-		temp = 0;
-		if (n >= 3)
-			for (j = 0; j < n; j++)
-				if (isg_poly_exists(j, digit, 2) == 0) {
-					if (digit[0] < j) num = isg_poly_find(digit[1] * n * n * (n + 1) + digit[0] * n + j, gl, G, err);
-					else if (digit[0] > j) num = isg_poly_find(digit[1] * n * n * (n + 1) + j * n + digit[0], gl, G, err);
-					temp = (float)(temp + PT_EXP((double)fr[num]) / 9.0 * self);
-					if (digit[1] < j) num = isg_poly_find(digit[0] * n * n * (n + 1) + digit[1] * n + j, gl, G, err);
-					else if (digit[1] > j) num = isg_poly_find(digit[0] * n * n * (n + 1) + j * n + digit[1], gl, G, err);
-					temp = (float)(temp + PT_EXP((double)fr[num]) / 9.0 * self);
-					num = isg_poly_find(j * n * n * (n + 1) + digit[1] * n + digit[0], gl, G, err);
-					temp = (float)(temp + PT_EXP((double)fr[num]) / 36.0 * self);
-					if (n >= 4)
-						for (k = j + 1; k < n; k++)
-							if (isg_poly_exists(k, digit, 2) == 0) {
-								num = isg_poly_find(isg_poly_calc_val2(digit, j, k, n), gl, G, err);
-								temp = (float)(temp + PT_EXP((double)fr[num]) / 36.0 * self);
-							}
-				}
-		fr[i] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[i]) + temp) - PT_LOG(1 - self / 2.0));
-		if (fr[i] > 0) *err |= 4;
-	}
-	tmp -= pc->g[3];
-	for (i = tmp - pc->g[2]; i < tmp; i++) { /* simplex iiij */
-		num = gl[i];
-		digit[0] = num % n;
-		num /= n;
-		digit[1] = num % n;
-		if (digit[0] < digit[1]) num = isg_poly_find((digit[0] * n * n + digit[1]) * (n + 1), gl, G, err);
-		else if (digit[0] > digit[1]) num = isg_poly_find((digit[1] * n * n + digit[0]) * (n + 1), gl, G, err);
-		temp = (float)(8.0 / 36.0 * PT_EXP((double)fr[num]) * self);
-		if (n >= 3)
-			for (j = 0; j < n; j++)
-				if (isg_poly_exists(j, digit, 2) == 0) {
-					if (digit[0] < j) num = isg_poly_find(digit[1] * n * n * (n + 1) + digit[0] * n + j, gl, G, err);
-					else if (digit[0] > j) num = isg_poly_find(digit[1] * n * n * (n + 1) + j * n + digit[0], gl, G, err);
-					temp = (float)(temp + PT_EXP((double)fr[num]) / 9.0 * self);
-				}
-		fr[i] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[i]) + temp) - PT_LOG(1 - self / 2.0));
-		if (fr[i] > 0) *err |= 4;
-	}
-	tmp -= pc->g[2];
-	for (i = tmp - pc->g[1]; i < tmp; i++) { /* mono iiii */
-		num = gl[i];
-		digit[0] = num % n;
-		temp = 0;
-		for (j = 0; j < n; j++)
-			if (j != digit[0]) {
-				num = isg_poly_find(digit[0] * n * (n * n + n + 1) + j, gl, G, err);
-				temp = (float)(temp + PT_EXP((double)fr[num]) / 4.0 * self);
-				/* sic: for digit[0] > j the reference repeats the digit[0] < j test in its else branch, so the
-				 * duplex term reuses the simplex index found above (poly_geno.c:1990-1996) */
-				if (digit[0] < j) num = isg_poly_find(digit[0] * n * n * (n + 1) + j * (n + 1), gl, G, err);
-				temp = (float)(temp + PT_EXP((double)fr[num]) / 36.0 * self);
-				if (n >= 3)
-					for (k = j + 1; k < n; k++)
-						if (k != digit[0]) {
-							num = isg_poly_find(digit[0] * n * n * (n + 1) + j * n + k, gl, G, err);
-							temp = (float)(temp + PT_EXP((double)fr[num]) / 36.0 * self);
-						}
-			}
-		fr[i] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[i]) + temp) - PT_LOG((double)(1 - self)));
-		if (fr[i] > 0) *err |= 4;
+	temp = vec[1];
+	for (j = 1; j <= tri; j++) vec[j] /= temp;
+	isg_poly_gaussj3(matr, vec, err);
+	for (j = 0; j < tri; j++) {
+		fr[r0 + j] = (float)(PT_LOG((double)vec[j + 1]) + PT_LOG((double)temp));
+		if (fr[r0 + j] > 0) *err |= 4;
 	}
 }
-
-/* calc_exfreq_allo (poly_geno.c:1592-1670) for one (cluster, locus): f / f2 = the cluster's allele frequencies in the two
- * subgenomes.  Copies 0, 1 (digits 3, 2 of the code) take f, copies 2, 3 take f2; float / double exactly as the reference. */
-ISG_HD void PT_NAME(exfreq_row_allo)(const isg_polyclass *pc, const double *f, const double *f2, float *ex)
+ISG_HD void PT_NAME(genfreq_duplex_at)(float self, const isg_polyclass *pc, const float *ex, float *fr, int r, int *err) /* iijj */
 {
-	const int n = pc->n;
-	int r;
-	for (r = 0; r < pc->G; r++) {
-		const int code = pc->list[r], d0 = code % n, d1 = (code / n) % n, d2 = (code / n / n) % n, d3 = code / n / n / n;
-		if (r < pc->g[1]) ex[r] = (float)((PT_LOG(f[d2]) + PT_LOG(f2[d0])) * 2);
-		else if (r < pc->g[1] + pc->g[2]) ex[r] = (float)(PT_LOG(2.0) + PT_LOG(f[d2]) * 2 + PT_LOG(f2[d0]) + PT_LOG(f2[d1]));
-		else if (r < pc->g[1] + pc->g[2] + pc->g[3]) ex[r] = (float)(PT_LOG(2.0) + PT_LOG(f2[d1]) * 2 + PT_LOG(f[d3]) + PT_LOG(f[d2]));
-		else {
-			ex[r] = (float)PT_LOG(4.0);
-			ex[r] += (float)PT_LOG(f2[d0]);
-			ex[r] += (float)PT_LOG(f2[d1]);
-			ex[r] += (float)PT_LOG(f[d2]);
-			ex[r] += (float)PT_LOG(f[d3]);
+	const int n = pc->n, d0 = pc->list[r] % n, d1 = (pc->list[r] / (n * n)) % n;
+	int x, y;
+	float temp = 0;
+	if (n >= 3)
+		for (x = 0; x < n; x++)
+			if (x != d0 && x != d1) {
+				temp = (float)(temp + PT_EXP((double)fr[isg_poly_rank(n, d1, d1, d0, x)]) / 9.0 * self);
+				temp = (float)(temp + PT_EXP((double)fr[isg_poly_rank(n, d0, d0, d1, x)]) / 9.0 * self);
+				temp = (float)(temp + PT_EXP((double)fr[isg_poly_rank(n, x, x, d1, d0)]) / 36.0 * self);
+				if (n >= 4)
+					for (y = x + 1; y < n; y++)
+						if (y != d0 && y != d1) temp = (float)(temp + PT_EXP((double)fr[isg_poly_rank(n, d0, d1, x, y)]) / 36.0 * self);
+			}
+	fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG(1 - self / 2.0));
+	if (fr[r] > 0) *err |= 4;
+}
+ISG_HD void PT_NAME(genfreq_simplex_at)(float self, const isg_polyclass *pc, const float *ex, float *fr, int r, int *err) /* iiij */
+{
+	const int n = pc->n, d0 = pc->list[r] % n, d1 = (pc->list[r] / n) % n; /* d1 is the tripled allele */
+	int x;
+	float temp = (float)(8.0 / 36.0 * PT_EXP((double)fr[isg_poly_rank(n, d0, d0, d1, d1)]) * self);
+	if (n >= 3)
+		for (x = 0; x < n; x++)
+			if (x != d0 && x != d1) temp = (float)(temp + PT_EXP((double)fr[isg_poly_rank(n, d1, d1, d0, x)]) / 9.0 * self);
+	fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG(1 - self / 2.0));
+	if (fr[r] > 0) *err |= 4;
+}
+ISG_HD void PT_NAME(genfreq_mono_at)(float self, const isg_polyclass *pc, const float *ex, float *fr, int r, int *err) /* iiii */
+{
+	const int n = pc->n, a = pc->list[r] % n;
+	int x, y, row;
+	float temp = 0;
+	for (x = 0; x < n; x++)
+		if (x != a) {
+			row = isg_poly_rank(n, a, a, a, x);
+			temp = (float)(temp + PT_EXP((double)fr[row]) / 4.0 * self);
+			/* sic: for a > x the reference repeats the a < x test in its else branch, so the duplex term reuses the
+			 * simplex row found above (poly_geno.c:1990-1996) */
+			if (a < x) row = isg_poly_rank(n, a, a, x, x);
+			temp = (float)(temp + PT_EXP((double)fr[row]) / 36.0 * self);
+			if (n >= 3)
+				for (y = x + 1; y < n; y++)
+					if (y != a) temp = (float)(temp + PT_EXP((double)fr[isg_poly_rank(n, a, a, x, y)]) / 36.0 * self);
 		}
-	}
+	fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG((double)(1 - self)));
+	if (fr[r] > 0) *err |= 4;
 }
 
-/* allo_genfreq (poly_geno.c:2122-2304) for one (cluster, locus): log genotype frequencies at selfing rate `self`, class by
- * class from ijkl down to iikk (each class only needs the ones solved before it); *err |= 4 when one comes out positive */
-ISG_HD void PT_NAME(genfreq_row_allo)(float self, const isg_polyclass *pc, const float *ex, float *fr, int *err)
+/* calc_exfreq_allo (poly_geno.c:1592-1670), row r: f / f2 = the cluster's allele frequencies in the two subgenomes.  Copies 0, 1
+ * (digits 3, 2 of the code) take f, copies 2, 3 take f2; float / double exactly as the reference. */
+ISG_HD float PT_NAME(exfreq_allo_at)(const isg_polyclass *pc, const double *f, const double *f2, int r)
 {
-	const int n = pc->n, b1 = pc->g[1], b2 = b1 + pc->g[2], b3 = b2 + pc->g[3];
-	int r, v, w;
-	float temp;
-	for (r = b3; r < pc->G; r++) { /* ijkl */
-		fr[r] = (float)(PT_LOG((double)(1 - self)) + ex[r] - PT_LOG((double)(1 - self / 4)));
-		if (fr[r] > 0) *err |= 4;
-	}
-	for (r = b2; r < b3; r++) { /* ijkk: the second subgenome's homozygote comes from selfed heterozygotes k v */
-		const int code = pc->list[r], k = code % n, b = (code / n / n) % n, a = code / n / n / n;
-		temp = 0;
+	const int n = pc->n, code = pc->list[r], d0 = code % n, d1 = (code / n) % n, d2 = (code / n / n) % n, d3 = code / n / n / n;
+	float ex;
+	if (r < pc->g[1]) return (float)((PT_LOG(f[d2]) + PT_LOG(f2[d0])) * 2);
+	if (r < pc->g[1] + pc->g[2]) return (float)(PT_LOG(2.0) + PT_LOG(f[d2]) * 2 + PT_LOG(f2[d0]) + PT_LOG(f2[d1]));
+	if (r < pc->g[1] + pc->g[2] + pc->g[3]) return (float)(PT_LOG(2.0) + PT_LOG(f2[d1]) * 2 + PT_LOG(f[d3]) + PT_LOG(f[d2]));
+	ex = (float)PT_LOG(4.0);
+	ex += (float)PT_LOG(f2[d0]);
+	ex += (float)PT_LOG(f2[d1]);
+	ex += (float)PT_LOG(f[d2]);
+	ex += (float)PT_LOG(f[d3]);
+	return ex;
+}
+
+/* allo_genfreq (poly_geno.c:2122-2304) at selfing rate self, row by row */
+ISG_HD void PT_NAME(genfreq_allo_ijkl_at)(float self, const float *ex, float *fr, int r, int *err)
+{
+	fr[r] = (float)(PT_LOG((double)(1 - self)) + ex[r] - PT_LOG((double)(1 - self / 4)));
+	if (fr[r] > 0) *err |= 4;
+}
+/* iikl (r below the ijkk rows) and ijkk: the homozygous subgenome comes from selfed heterozygotes a v / k v -- ijkl rows only */
+ISG_HD void PT_NAME(genfreq_allo_het_at)(float self, const isg_polyclass *pc, const float *ex, float *fr, int r, int *err)
+{
+	const int n = pc->n, code = pc->list[r];
+	int v;
+	float temp = 0;
+	if (r >= pc->g[1] + pc->g[2]) { /* ijkk */
+		const int k = code % n, b = (code / n / n) % n, a = code / n / n / n;
 		for (v = 0; v < n; v++)
 			if (v != k) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, b, k, v)]) * self / 8.0);
-		fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG(1 - self / 2.0));
-		if (fr[r] > 0) *err |= 4;
-	}
-	for (r = b1; r < b2; r++) { /* iikl */
-		const int code = pc->list[r], d = code % n, c = (code / n) % n, a = (code / n / n) % n;
-		temp = 0;
+	} else { /* iikl */
+		const int d = code % n, c = (code / n) % n, a = (code / n / n) % n;
 		for (v = 0; v < n; v++)
 			if (v != a) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, v, c, d)]) * self / 8.0);
-		fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG(1 - self / 2.0));
-		if (fr[r] > 0) *err |= 4;
 	}
-	for (r = 0; r < b1; r++) { /* iikk */
-		const int code = pc->list[r], k = code % n, a = (code / n / n) % n;
-		temp = 0;
-		for (v = 0; v < n; v++)
-			if (v != k) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, a, k, v)]) * self / 4.0);
-		for (v = 0; v < n; v++)
-			if (v != a) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, v, k, k)]) * self / 4.0);
-		for (v = 0; v < n; v++)
-			for (w = 0; w < n; w++)
-				if (v != a && w != k) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, v, k, w)]) * self / 16.0);
-		fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG((double)(1 - self)));
-		if (fr[r] > 0) *err |= 4;
-	}
+	fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG(1 - self / 2.0));
+	if (fr[r] > 0) *err |= 4;
+}
+ISG_HD void PT_NAME(genfreq_allo_iikk_at)(float self, const isg_polyclass *pc, const float *ex, float *fr, int r, int *err)
+{
+	const int n = pc->n, code = pc->list[r], k = code % n, a = (code / n / n) % n;
+	int v, w;
+	float temp = 0;
+	for (v = 0; v < n; v++)
+		if (v != k) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, a, k, v)]) * self / 4.0);
+	for (v = 0; v < n; v++)
+		if (v != a) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, v, k, k)]) * self / 4.0);
+	for (v = 0; v < n; v++)
+		for (w = 0; w < n; w++)
+			if (v != a && w != k) temp = (float)(temp + PT_EXP((double)fr[isg_allo_row_any(n, a, v, k, w)]) * self / 16.0);
+	fr[r] = (float)(PT_LOG((1 - self) * PT_EXP((double)ex[r]) + temp) - PT_LOG((double)(1 - self)));
+	if (fr[r] > 0) *err |= 4;
+}
+
+/* ---- whole tables for one (cluster, locus), serially: every row, the genfreq classes in dependency order ---- */
+ISG_HD void PT_NAME(exfreq_row)(const isg_polyclass *pc, const double *f, float *ex)
+{
+	int r;
+	for (r = 0; r < pc->G; r++) ex[r] = PT_NAME(exfreq_at)(pc, f, r);
+}
+ISG_HD void PT_NAME(genfreq_row)(float self, const isg_polyclass *pc, const float *ex, float *fr, int *err)
+{
+	const int b1 = pc->g[1], b2 = b1 + pc->g[2], b3 = b2 + pc->g[3], b4 = b3 + pc->g[4];
+	int r;
+	for (r = b4; r < pc->G; r++) PT_NAME(genfreq_quadri_at)(self, ex, fr, r, err);
+	for (r = b3; r < b4; r += 3) PT_NAME(genfreq_tri_at)(self, pc, ex, fr, r, err);
+	for (r = b2; r < b3; r++) PT_NAME(genfreq_duplex_at)(self, pc, ex, fr, r, err);
+	for (r = b1; r < b2; r++) PT_NAME(genfreq_simplex_at)(self, pc, ex, fr, r, err);
+	for (r = 0; r < b1; r++) PT_NAME(genfreq_mono_at)(self, pc, ex, fr, r, err);
+}
+ISG_HD void PT_NAME(exfreq_row_allo)(const isg_polyclass *pc, const double *f, const double *f2, float *ex)
+{
+	int r;
+	for (r = 0; r < pc->G; r++) ex[r] = PT_NAME(exfreq_allo_at)(pc, f, f2, r);
+}
+ISG_HD void PT_NAME(genfreq_row_allo)(float self, const isg_polyclass *pc, const float *ex, float *fr, int *err)
+{
+	const int b1 = pc->g[1], b3 = b1 + pc->g[2] + pc->g[3];
+	int r;
+	for (r = b3; r < pc->G; r++) PT_NAME(genfreq_allo_ijkl_at)(self, ex, fr, r, err);
+	for (r = b1; r < b3; r++) PT_NAME(genfreq_allo_het_at)(self, pc, ex, fr, r, err);
+	for (r = 0; r < b1; r++) PT_NAME(genfreq_allo_iikk_at)(self, pc, ex, fr, r, err);
 }

@@ -19,11 +19,14 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DUMP = os.path.join(orc.ORC_DIR, "orc_dump_poly")
 
-# name: (N, L, K, allele counts per locus, missing, u, b, t, e, r, j, seeds, allo).  The oracle finds rows by linear search: about
-# 45 s per 30-allele autotetraploid locus for 2 iterations at K = 2, so one such locus per case and all oracle runs started at once.
+# name: (N, L, K, allele counts per locus, missing, u, b, t, e, r, j, seeds, allo).  The oracle finds rows in closed form as the kernels do
+# (one run is well under a second); all oracle runs are started at once.  wa_auto_e0: K = 3 and -e 0 (selfing rates reach exactly 0 and 1),
+# a locus at the 32-allele cap, one at the 17-allele floor of the wide path (classes below and above 256 rows: single- and multi-trip
+# strided loops), and 3 and 1 alleles for the n >= 3 / n >= 4 guards.
 WIDE = {
     "wa_auto": (40, 7, 2, (32, 17, 24, 1, 2, 3, 4), 0.03, 2, 1, 1, 1, 1, 1, (51, 7, 1999), False),
     "wa_allo": (40, 6, 2, (32, 18, 23, 1, 2, 4), 0.03, 2, 1, 1, 0, 1, 1, (52, 8, 2000), True),
+    "wa_auto_e0": (40, 5, 3, (32, 20, 17, 3, 1), 0.03, 2, 1, 1, 0, 1, 1, (53, 9, 2001), False),
 }
 
 
