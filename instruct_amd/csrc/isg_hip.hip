@@ -47,6 +47,7 @@
 #include "isg_host_dirichlet.h"
 #include "isg_kdispatch.h"
 #include "isg_devbuf.h"
+#include "isg_ahead.h"
 
 #define ISG_KCAP 32  /* K of the register-resident kernel instances, and of ploidy 4 */
 #define ISG_KWIDE 64 /* diploid K above ISG_KCAP: the K-generic wide kernels (DESIGN.md §4 "K up to 64") */
@@ -165,6 +166,8 @@ struct CtxBufs {
 	PinnedBuf<double> htape;           /* replay update_P: the host loop's uniforms (host_tape_begin); pinned: a 2 MB copy per sweep */
 	DevEvent ev_tape;                  /* ... the tape has arrived (update_P_ahead) */
 	DevEvent ev_cnt;                   /* replay update_P: the counts have arrived (the tape is still on its way) */
+	PinnedBuf<unsigned char> mail;     /* what the host looks of the replay iteration copy back: a slot per look (MAIL_*), alpha's ratios last */
+	DevEvent ev_look[AH_NLOOKS];       /* look l's copies into its slot have arrived */
 	/* CHAIN running means kept on the device (isg_store_*): qq, qq2 [N][K]; indvlkh, gen, gen2 [N]; freq, freq2 in the
 	 * device order of d.freq */
 	DevBuf<double> st_qq, st_qq2, st_lkh, st_gen, st_gen2, st_freq, st_freq2;
@@ -219,7 +222,10 @@ struct isg_ctx : CtxBufs {
 	int spop_tree = 1;                    /* INSTRUCT_SPOP_TREE=0: the one-workgroup k_spop always */
 	int test_abort = 0;                   /* INSTRUCT_ZQ_TEST_ABORT=n: the n-th cooperative sweep is treated as aborted (tests) */
 	long zq_fallbacks = 0;                /* sweeps redone by the single-workgroup kernel */
-	hvec<double> ratios_h;
+	AheadState ah;                        /* results enqueued ahead of a look, and looks not waited for yet (isg_ahead.h) */
+	bool lookahead = true;                /* INSTRUCT_LOOKAHEAD=0: isg_iteration enqueues every sweep's kernels where the sweep itself would */
+	bool la_on = false;                   /* inside isg_iteration with lookahead set: independent work goes between a look's event and its wait */
+	bool zq_pro_ready = false;            /* AH_EXPECT: the prologue ran as far as k_wk_centers (false: it found the interval path closed this sweep) */
 	/* which host mirrors are current */
 	bool h_qq, h_gen, h_S, h_lkh;
 	long st_step = 0;
@@ -1941,6 +1947,33 @@ static void pin_host(isg_ctx *c, void *ptr, size_t bytes)
 	if (ptr && bytes && hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess) c->pinned.push_back(ptr);
 	else (void)hipGetLastError();
 }
+/* The mailbox: slots of the pinned block a look's device-to-host copies land in (they outlive the function that asked for them, and a
+ * copy into pinned memory is queued, not staged: the host gets on with enqueueing whatever does not depend on the answer).  The look's
+ * event is recorded right behind its copies; the host waits for that event, not for the stream. */
+enum { MAIL_P = 0, MAIL_G = 2048, MAIL_ZQ = 2560, MAIL_RATIOS = 4096 };
+struct MailG { uint64_t used; unsigned err[4]; };
+template <class T> static T *mail_slot(isg_ctx *c, size_t off) { return (T *)(c->mail.get() + off); }
+static int look_record(isg_ctx *c, int look)
+{
+	if (!c->ev_look[look]) HIPCHK(hipEventCreateWithFlags(&c->ev_look[look].e, hipEventDisableTiming));
+	HIPCHK(hipEventRecord(c->ev_look[look], c->stream));
+	ahead_look_recorded(&c->ah, look);
+	return 0;
+}
+static int look_wait(isg_ctx *c, int look)
+{
+	HIPCHK(hipEventSynchronize(c->ev_look[look]));
+	ahead_look_waited(&c->ah, look);
+	return 0;
+}
+/* every public entry point and getter starts here: looks somebody recorded and did not wait for are waited for (none, as a rule) */
+static int settle(isg_ctx *c)
+{
+	const unsigned m = ahead_settle(&c->ah);
+	for (int l = 0; m && l < AH_NLOOKS; l++)
+		if (m & (1u << l)) HIPCHK(hipEventSynchronize(c->ev_look[l]));
+	return 0;
+}
 #define HOST_T(c, k, t0) do { if ((c)->host_timing) { const auto t1_ = std::chrono::steady_clock::now(); (c)->host_t[k] += std::chrono::duration<double>(t1_ - (t0)).count(); (t0) = t1_; } } while (0)
 /*
  * The sequential host loop of replay update_P, for every kind of chain (diploid; autotetraploid; allotetraploid: `second` gives the
@@ -2017,6 +2050,10 @@ static bool fits_resident(Kern kern, int threads, long blocks, int device)
  * chain-iterations/s), so it is only used by a device's sole context */
 static std::atomic<int> g_live_ctx[64];
 static void ctx_count(isg_ctx *c, int delta);
+static int launch_lkh_sweep(isg_ctx *c);
+static void launch_lkh_total(isg_ctx *c);
+static int lkh_total_ahead(isg_ctx *c);
+static bool lkh_sweep_is_generic(const isg_ctx *c);
 #include "isg_resolve_hip.inc"
 #include "isg_walk_hip.inc"
 #include "isg_spec_hip.inc"
@@ -2073,6 +2110,10 @@ static int ctx_init_common(isg_ctx *c, const std::vector<int> &nvalid, int Lp, i
 	c->prof = false;
 	c->host_timing = env_flag(getenv("INSTRUCT_HOST_TIMING"), false);
 	c->host_tape = env_flag(getenv("INSTRUCT_HOST_TAPE"), true);
+	c->lookahead = env_flag(getenv("INSTRUCT_LOOKAHEAD"), true);
+	ahead_init(&c->ah);
+	HIPCHK(c->mail.alloc(MAIL_RATIOS + (c->cfg.P == 2 ? sizeof(double) * (size_t)N * K : 0)));
+	memset(c->mail.get(), 0, MAIL_RATIOS);
 	c->h_qq = c->h_gen = c->h_S = c->h_lkh = true;
 	isg_wh_tables_init(&c->tab_h);
 	HIPCHK(c->d_tab.upload(&c->tab_h, 1));
@@ -2205,7 +2246,6 @@ extern "C" int isg_ctx_create(const isg_config *cfg, const int32_t *allelenum, c
 	HIPCHK(c->d_state.alloc_zero(ISG_KWIDE));
 	HIPCHK(c->d_ratios.alloc_zero((size_t)N * K));
 	HIPCHK(c->d_total.alloc_zero(1));
-	c->ratios_h.assign((size_t)N * K, 0.0);
 	keyed_layout(c);
 	if (cfg->mode == 0 && !d.lftab) return fail("isg_ctx_create: mode 0 needs its log frequency table (INSTRUCT_LL_TABLES must not be 0)");
 	if (cfg->mode == 4) {
@@ -2227,6 +2267,7 @@ extern "C" int isg_set_seeds(isg_ctx *c, long s1, long s2, long s3)
 }
 extern "C" int isg_get_seeds(isg_ctx *c, long s[3])
 {
+	if (settle(c)) return 1;
 	if (c->raw_valid) { s[0] = c->raw_seed[0]; s[1] = c->raw_seed[1]; s[2] = c->raw_seed[2]; }
 	else { s[0] = c->rng.s1; s[1] = c->rng.s2; s[2] = c->rng.s3; }
 	return 0;
@@ -2270,6 +2311,7 @@ static int refresh_freqf(isg_ctx *c)
 }
 static int download_freq(isg_ctx *c)
 {
+	if (settle(c)) return 1;
 	const int L = c->cfg.L, K = c->cfg.K, A = c->Amax, KP = c->d.KP;
 	HIPCHK(hipMemcpyAsync(c->freq_stage.data(), c->d.freq, sizeof(double) * (size_t)L * A * KP, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -2279,6 +2321,7 @@ static int download_freq(isg_ctx *c)
 /* host mirrors are refreshed on demand only (getters, the host-side steps of the replay schedule) */
 static int ensure_qq(isg_ctx *c)
 {
+	if (settle(c)) return 1;
 	if (c->h_qq) return 0;
 	HIPCHK(hipMemcpyAsync(c->qq.data(), c->d.qq, sizeof(double) * c->qq.size(), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipMemcpyAsync(c->qqnum.data(), c->d.qqnum, sizeof(int) * c->qqnum.size(), hipMemcpyDeviceToHost, c->stream));
@@ -2288,6 +2331,7 @@ static int ensure_qq(isg_ctx *c)
 }
 static int ensure_gen(isg_ctx *c)
 {
+	if (settle(c)) return 1;
 	if (c->h_gen) return 0;
 	HIPCHK(hipMemcpyAsync(c->gen.data(), c->d.gen, sizeof(int) * c->gen.size(), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -2296,6 +2340,7 @@ static int ensure_gen(isg_ctx *c)
 }
 static int ensure_S(isg_ctx *c)
 {
+	if (settle(c)) return 1;
 	if (c->h_S) return 0;
 	HIPCHK(hipMemcpyAsync(c->S.data(), c->d_S, sizeof(double) * c->S.size(), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipMemcpyAsync(c->state.data(), c->d_state, sizeof(int) * c->cfg.K, hipMemcpyDeviceToHost, c->stream));
@@ -2305,6 +2350,7 @@ static int ensure_S(isg_ctx *c)
 }
 static int ensure_lkh(isg_ctx *c)
 {
+	if (settle(c)) return 1;
 	if (c->h_lkh) return 0;
 	unsigned e[4] = {0, 0, 0, 0};
 	HIPCHK(hipMemcpyAsync(c->indvlkh.data(), c->d.indvlkh, sizeof(double) * c->indvlkh.size(), hipMemcpyDeviceToHost, c->stream));
@@ -2373,8 +2419,23 @@ static int update_P_ahead(isg_ctx *c)
 	c->ahead_valid = false;
 	if (c->poly || is_keyed(c) || !c->host_tape) return 0;
 	if (c->pdev && c->pdev->usable) return 0; /* update_P runs on the device: nothing for the host to get ahead with */
+	if (ahead_has(&c->ah, AH_COUNTS)) return 0; /* (isg_iteration's launch-ahead has taken the counts already) */
 	if (launch_count(c)) return 1;
 	return host_update_P(c, HOSTP_REQUEST, c->d.cnt, nullptr, true);
+}
+/* Launch-ahead behind update_alpha's look (isg_iteration only): Z is final, so the next update_P's counts -- and, where update_P runs on the
+ * device, their gather and scan into stream order -- are enqueued while the host still waits for the ratios.  None of them takes a
+ * stream position.  The host-loop path keeps update_P_ahead's request, which needs the position update_alpha leaves. */
+static int counts_ahead(isg_ctx *c)
+{
+	if (!c->la_on || c->poly) return 0;
+	const bool dev = c->pdev && c->pdev->usable;
+	if (!is_keyed(c) && !dev) return 0;
+	if (launch_count(c)) return 1;
+	if (!is_keyed(c)) pdev_launch_prep(c, c->pdev);
+	HIPCHK(hipGetLastError());
+	ahead_set(&c->ah, AH_COUNTS);
+	return 0;
 }
 
 /* ---- update_P ---- */
@@ -2382,12 +2443,16 @@ extern "C" int isg_update_P(isg_ctx *c)
 {
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (c->poly) return poly_update_P(c);
+	if (settle(c)) return 1;
 	DevView &d = c->d;
 	const int L = c->cfg.L, K = c->cfg.K;
 	/* requested at the end of the previous iteration's update_alpha (update_P_ahead), for exactly this stream position? */
 	const bool ahead = c->ahead_valid && !is_keyed(c) && c->ahead_rng.s1 == c->rng.s1 && c->ahead_rng.s2 == c->rng.s2 && c->ahead_rng.s3 == c->rng.s3;
 	c->ahead_valid = false;
-	if (!ahead && launch_count(c)) return 1;
+	/* taken behind update_alpha's look (counts_ahead), and nothing has written Z since? */
+	const bool counted = ahead_take(&c->ah, AH_COUNTS);
+	ahead_wrote_freq(&c->ah);
+	if (!ahead && !counted && launch_count(c)) return 1;
 	if (is_keyed(c)) {
 		int n = K * L, B = 256;
 		prof_begin(c);
@@ -2401,8 +2466,8 @@ extern "C" int isg_update_P(isg_ctx *c)
 	 * missed, more alleles at a locus than the engine's groups hold) they are drawn sequentially on the host from the counts */
 	if (!ahead && c->pdev && c->pdev->usable) {
 		bool done = false;
-		if (pdev_update_P(c, c->pdev, &done)) return 1;
-		if (done) return refresh_freqf(c);
+		if (pdev_update_P(c, c->pdev, &done, counted)) return 1;
+		if (done) return ahead_take(&c->ah, AH_FREQF) ? 0 : refresh_freqf(c); /* (enqueued behind the look already) */
 	}
 	if (host_update_P(c, ahead ? HOSTP_DRAW : HOSTP_REQUEST | HOSTP_DRAW, d.cnt, nullptr, true)) return 1;
 	auto ht0 = std::chrono::steady_clock::now();
@@ -2422,6 +2487,7 @@ extern "C" int isg_update_S_POP(isg_ctx *c)
 	if (c->cfg.mode != 2) return 0;
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (c->poly) return poly_update_S_POP(c);
+	if (settle(c)) return 1;
 	const int K = c->cfg.K;
 	isg_wh start = is_keyed(c) ? isg_wh_jump(&c->tab_h, c->origin, iter_base(c) + c->ky[KY_OFFS]) : c->rng;
 	if (c->cfg.back_refl == 1 && K <= ISG_SPOP_TREE_K && c->spop_tree) {
@@ -2457,6 +2523,8 @@ extern "C" int isg_update_G(isg_ctx *c)
 	NOT_POLY(c, "isg_update_G");
 	if (c->cfg.mode != 2 && c->cfg.mode != 3) return 0;
 	HIPCHK(hipSetDevice(c->cfg.device));
+	if (settle(c)) return 1;
+	ahead_wrote_gen(&c->ah);
 	DevView &d = c->d;
 	double *d_S = c->d_S;
 	isg_wh base = is_keyed(c) ? isg_wh_jump(&c->tab_h, c->origin, iter_base(c) + c->ky[KY_OFFG]) : c->rng;
@@ -2473,13 +2541,15 @@ extern "C" int isg_update_G(isg_ctx *c)
 	HIPCHK(hipGetLastError());
 	c->h_gen = false;
 	if (!is_keyed(c)) {
-		uint64_t used = 0;
-		unsigned e[4] = {0, 0, 0, 0};
-		HIPCHK(hipMemcpyAsync(&used, c->d_pos, sizeof(used), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipMemcpyAsync(e, c->d_err, sizeof(e), hipMemcpyDeviceToHost, c->stream)); /* same wait: dt_stat out of range (mcmc.c:1524-1546) */
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (report_dev_err(e)) return 1;
-		host_advance(c, used);
+		MailG *m = mail_slot<MailG>(c, MAIL_G);
+		HIPCHK(hipMemcpyAsync(&m->used, c->d_pos, sizeof(m->used), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(m->err, c->d_err, sizeof(m->err), hipMemcpyDeviceToHost, c->stream)); /* same wait: dt_stat out of range (mcmc.c:1524-1546) */
+		if (look_record(c, AH_LOOK_G)) return 1;
+		/* launch-ahead: the part of the coming update_ZQ that does not take the stream position this look delivers */
+		if (c->la_on && c->zspec && spec_ZQ_prologue_ahead(c, c->zspec)) return 1;
+		if (look_wait(c, AH_LOOK_G)) return 1;
+		if (report_dev_err(m->err)) return 1;
+		host_advance(c, m->used);
 	}
 	return 0; /* keyed schedule: no host wait here; the flag is read with the next likelihood download (ensure_lkh) */
 }
@@ -2551,6 +2621,10 @@ extern "C" int isg_update_ZQ(isg_ctx *c, int init_flag)
 	c->ahead_valid = false; /* Z changes: counts requested ahead are stale */
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (c->poly) return poly_update_ZQ(c, init_flag);
+	if (settle(c)) return 1;
+	const bool prologue = ahead_take(&c->ah, AH_EXPECT) && !init_flag; /* (before the writes below make it stale: it is this sweep's own) */
+	ahead_wrote_z(&c->ah);
+	ahead_wrote_qq(&c->ah);
 	const int K = c->cfg.K;
 	bool chain = !is_keyed(c);
 	isg_wh base = chain ? c->rng : c->origin;
@@ -2560,7 +2634,7 @@ extern "C" int isg_update_ZQ(isg_ctx *c, int init_flag)
 	c->d.tape_len = 0;
 	if (chain && !init_flag && c->zspec) { /* the start positions resolved from intervals of shapes, then one parallel sweep (isg_spec_hip.inc) */
 		bool done = false;
-		if (spec_update_ZQ(c, c->zspec, base, &done)) return 1;
+		if (spec_update_ZQ(c, c->zspec, base, &done, prologue)) return 1;
 		if (done) return 0;
 	}
 	if (chain && !init_flag && c->rs) { /* the start positions resolved block-wise, then one parallel sweep (isg_resolve_hip.inc) */
@@ -2640,6 +2714,7 @@ extern "C" int isg_update_alpha(isg_ctx *c)
 {
 	NOT_POLY(c, "isg_update_alpha");
 	HIPCHK(hipSetDevice(c->cfg.device));
+	if (settle(c)) return 1;
 	const size_t NK = (size_t)c->cfg.N * c->cfg.K;
 	if (is_keyed(c)) host_seek(c, iter_base(c) + c->ky[KY_OFFA]);
 	isg_cursor cur;
@@ -2654,13 +2729,17 @@ extern "C" int isg_update_alpha(isg_ctx *c)
 		hipLaunchKernelGGL(k_alpha_ratios, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, c->stream, c->d, ralpha, c->alpha, c->d_ratios);
 		prof_end(c, "k_alpha_ratios");
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(c->ratios_h.data(), c->d_ratios, sizeof(double) * NK, hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
+		double *ratios_h = mail_slot<double>(c, MAIL_RATIOS);
+		HIPCHK(hipMemcpyAsync(ratios_h, c->d_ratios, sizeof(double) * NK, hipMemcpyDeviceToHost, c->stream));
+		if (look_record(c, AH_LOOK_ALPHA)) return 1;
+		if (lkh_total_ahead(c) || counts_ahead(c)) return 1; /* launch-ahead: what needs neither alpha nor the stream position */
+		if (look_wait(c, AH_LOOK_ALPHA)) return 1;
 		double mh = 1.0;
-		for (size_t k = 0; k < NK; k++) mh *= c->ratios_h[k]; /* in the reference's order: overflow to inf, 0 and NaN included */
+		for (size_t k = 0; k < NK; k++) mh *= ratios_h[k]; /* in the reference's order: overflow to inf, 0 and NaN included */
 		double thr = (1 > mh) ? mh : 1;
 		c->alpha = (host_next(c) < thr) ? ralpha : c->alpha;
-	}
+	} else if (lkh_total_ahead(c) || counts_ahead(c)) return 1;
+	ahead_wrote_alpha(&c->ah);
 	return update_P_ahead(c);
 }
 
@@ -2672,6 +2751,19 @@ extern "C" int isg_cal_lkh(isg_ctx *c)
 	if (c->cfg.mode == 0) return noadm_cal_lkh(c);
 	if (c->cfg.mode == 4) return inbreed_cal_lkh(c);
 	if (c->cfg.mode == 5) return indiv_cal_lkh_F(c);
+	if (settle(c)) return 1;
+	const bool total = ahead_has(&c->ah, AH_LKH_TOTAL); /* (the total goes with the sweep it summed: asked before the sweep is taken) */
+	const bool swept = ahead_take(&c->ah, AH_LKH);
+	if (!swept && launch_lkh_sweep(c)) return 1;
+	if (!swept || !total) launch_lkh_total(c);
+	HIPCHK(hipGetLastError());
+	c->h_lkh = false;
+	return 0;
+}
+/* cal_lkh's two kernels.  The sweep reads Z, qq, the generations and the tables; the total the sweep's indvlkh. */
+static bool lkh_sweep_is_generic(const isg_ctx *c) { return !c->poly && c->cfg.mode != 0 && c->cfg.mode != 4 && c->cfg.mode != 5; }
+static int launch_lkh_sweep(isg_ctx *c)
+{
 	DevView &d = c->d;
 	prof_begin(c);
 	if (d.lli && d.mode == 2) hipLaunchKernelGGL((k_loglik_int<256, false>), dim3(d.N), dim3(256), 0, c->stream, d);
@@ -2679,11 +2771,22 @@ extern "C" int isg_cal_lkh(isg_ctx *c)
 	else if (d.K > ISG_KCAP) hipLaunchKernelGGL((k_loglik_w<256, false>), dim3(d.N), dim3(256), 0, c->stream, d);
 	else hipLaunchKernelGGL((k_loglik<256, false>), dim3(d.N), dim3(256), 0, c->stream, d);
 	prof_end(c, "k_loglik_lkh");
-	prof_begin(c);
-	hipLaunchKernelGGL(k_lkh_total<1024>, dim3(1), dim3(1024), 0, c->stream, d, c->d_total);
-	prof_end(c, "k_lkh_total");
 	HIPCHK(hipGetLastError());
-	c->h_lkh = false;
+	return 0;
+}
+static void launch_lkh_total(isg_ctx *c)
+{
+	prof_begin(c);
+	hipLaunchKernelGGL(k_lkh_total<1024>, dim3(1), dim3(1024), 0, c->stream, c->d, c->d_total);
+	prof_end(c, "k_lkh_total");
+}
+/* launch-ahead behind update_alpha's look: the total of a likelihood sweep that ran behind update_ZQ's look */
+static int lkh_total_ahead(isg_ctx *c)
+{
+	if (!c->la_on || !ahead_has(&c->ah, AH_LKH)) return 0;
+	launch_lkh_total(c);
+	HIPCHK(hipGetLastError());
+	ahead_set(&c->ah, AH_LKH_TOTAL);
 	return 0;
 }
 
@@ -2719,6 +2822,8 @@ extern "C" int isg_update_Z(isg_ctx *c, int init_flag) /* mode 0: update_Z, mcmc
 	c->ahead_valid = false; /* Z changes: counts requested ahead are stale */
 	if (c->poly || c->cfg.mode != 0) return fail("isg_update_Z: mode 0 (-v 0) only");
 	HIPCHK(hipSetDevice(c->cfg.device));
+	if (settle(c)) return 1;
+	ahead_wrote_z(&c->ah);
 	return noadm_update_Z(c, init_flag);
 }
 
@@ -2737,6 +2842,12 @@ extern "C" int isg_iteration(isg_ctx *c)
 		HIPCHK(hipSetDevice(c->cfg.device));
 		return poly_iteration(c);
 	}
+	/* the sweeps below enqueue independent work of the NEXT sweep between a look's event and its wait (INSTRUCT_LOOKAHEAD=0: they do not) */
+	struct LaScope {
+		isg_ctx *c;
+		explicit LaScope(isg_ctx *p) : c(p) { c->la_on = c->lookahead; }
+		~LaScope() { c->la_on = false; ahead_end_iteration(&c->ah); }
+	} la_scope(c);
 	if (isg_update_P(c)) return 1;
 	if (c->cfg.mode == 0) { /* mcmc.c:113-115 */
 		if (isg_update_Z(c, 0)) return 1;
@@ -2774,6 +2885,8 @@ extern "C" int isg_chain_init(isg_ctx *c, const float *initd)
 	c->ahead_valid = false; /* Z changes: counts requested ahead are stale */
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (c->poly) return poly_chain_init(c, initd);
+	if (settle(c)) return 1;
+	ahead_chain_init(&c->ah);
 	const int N = c->cfg.N, K = c->cfg.K;
 	c->origin = c->rng;
 	c->iter = 0;
@@ -2854,6 +2967,7 @@ extern "C" int isg_get_z(isg_ctx *c, int32_t *z)
 {
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (c->poly) return poly_get_bytes(c, c->poly->p.z, z);
+	if (settle(c)) return 1;
 	const int N = c->cfg.N, L = c->cfg.L, Lp = c->d.Lp;
 	std::vector<uint8_t> h((size_t)N * Lp * 2);
 	HIPCHK(hipMemcpyAsync(h.data(), c->d.z, h.size(), hipMemcpyDeviceToHost, c->stream));
@@ -2866,6 +2980,8 @@ extern "C" int isg_set_z(isg_ctx *c, const int32_t *z)
 	c->ahead_valid = false; /* Z changes: counts requested ahead are stale */
 	NOT_POLY(c, "isg_set_z");
 	HIPCHK(hipSetDevice(c->cfg.device));
+	if (settle(c)) return 1;
+	ahead_wrote_z(&c->ah);
 	const int N = c->cfg.N, L = c->cfg.L, Lp = c->d.Lp;
 	std::vector<uint8_t> h((size_t)N * Lp * 2, 0xff);
 	for (int i = 0; i < N; i++)
@@ -2889,6 +3005,8 @@ extern "C" int isg_set_freq(isg_ctx *c, const double *f)
 {
 	NOT_POLY(c, "isg_set_freq");
 	HIPCHK(hipSetDevice(c->cfg.device));
+	if (settle(c)) return 1;
+	ahead_wrote_freq(&c->ah);
 	memcpy(c->freq.data(), f, sizeof(double) * c->freq.size());
 	if (upload_freq(c)) return 1;
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -2905,6 +3023,7 @@ extern "C" int isg_set_qq(isg_ctx *c, const double *q)
 {
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (ensure_qq(c)) return 1; /* keeps qqnum */
+	ahead_wrote_qq(&c->ah);
 	memcpy(c->qq.data(), q, sizeof(double) * c->qq.size());
 	HIPCHK(hipMemcpy(c->d.qq, q, sizeof(double) * c->qq.size(), hipMemcpyHostToDevice));
 	return 0;
@@ -2928,6 +3047,8 @@ extern "C" int isg_set_generation(isg_ctx *c, const int32_t *g)
 {
 	NOT_POLY(c, "isg_set_generation");
 	HIPCHK(hipSetDevice(c->cfg.device));
+	if (settle(c)) return 1;
+	ahead_wrote_gen(&c->ah);
 	memcpy(c->gen.data(), g, sizeof(int) * c->gen.size());
 	HIPCHK(hipMemcpy(c->d.gen, g, sizeof(int) * c->gen.size(), hipMemcpyHostToDevice));
 	c->h_gen = true;
@@ -2962,8 +3083,19 @@ extern "C" int isg_get_indvlkh(isg_ctx *c, double *v)
 	memcpy(v, c->indvlkh.data(), sizeof(double) * c->indvlkh.size());
 	return 0;
 }
-extern "C" int isg_get_alpha(isg_ctx *c, double *a) { *a = c->alpha; return 0; }
-extern "C" int isg_set_alpha(isg_ctx *c, double a) { c->alpha = a; return 0; }
+extern "C" int isg_get_alpha(isg_ctx *c, double *a)
+{
+	if (settle(c)) return 1;
+	*a = c->alpha;
+	return 0;
+}
+extern "C" int isg_set_alpha(isg_ctx *c, double a)
+{
+	if (settle(c)) return 1;
+	ahead_wrote_alpha(&c->ah);
+	c->alpha = a;
+	return 0;
+}
 extern "C" int isg_get_totallkh(isg_ctx *c, double *t)
 {
 	HIPCHK(hipSetDevice(c->cfg.device));

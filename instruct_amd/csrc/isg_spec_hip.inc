@@ -357,14 +357,28 @@ static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid
 	return 0;
 }
 
-/* launch_expect(alo, ahi) / launch_probe(grid) / launch_at(): the ploidy's kernels.  *done = false: nothing is changed (qq restored),
- * the caller takes its other paths. */
-template <class LE, class LP, class LA>
-static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done, LE launch_expect, LP launch_probe, LA launch_at, bool second, bool *again)
+/* what update_ZQ's look brings back (the mailbox's slot MAIL_ZQ) */
+struct MailZQ {
+	struct { unsigned done, fail; unsigned long long total; } r;
+	WkState st;
+	SpecDev dev;
+	unsigned err[4];
+};
+static_assert(sizeof(MailZQ) <= MAIL_RATIOS - MAIL_ZQ, "update_ZQ's slot of the mailbox");
+
+static WalkInputs spec_inputs(const SpecCtx *sp, isg_wh base)
 {
-	*done = false;
-	*again = false;
-	if (!sp) return 0;
+	WalkInputs in;
+	in.gam0 = sp->d_gam0; in.gpos = sp->d_gpos; in.gcnt = nullptr; in.alo = sp->d_alo; in.ahi = sp->d_ahi; in.base = base;
+	return in;
+}
+/* The part of a sweep that takes no stream position: whether the path runs at all this sweep, the plan, the state words zeroed, qq saved,
+ * the intervals of shapes and the windows' centres (WkCenterArgs has no base).  It is valid for the coming sweep only.  *ready = false: the
+ * interval path sits this sweep out.  update_G's look runs it ahead (spec_ZQ_prologue_ahead); walk_prepare may wait for the stream. */
+template <class LE>
+static int spec_ZQ_prologue(isg_ctx *c, SpecCtx *sp, LE launch_expect, bool second, bool *ready)
+{
+	*ready = false;
 	if (!second && sp->cooldown > 0) { sp->cooldown--; return 0; }
 	const int N = sp->N, K = sp->K;
 	WalkRun &w = sp->walk;
@@ -379,10 +393,29 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 	prof_begin(c);
 	launch_expect(sp->d_alo, sp->d_ahi);
 	prof_end(c, "k_zexpect");
-	WalkInputs in;
-	in.gam0 = sp->d_gam0; in.gpos = sp->d_gpos; in.gcnt = nullptr; in.alo = sp->d_alo; in.ahi = sp->d_ahi; in.base = base;
+	isg_wh nobase;
+	nobase.s1 = nobase.s2 = nobase.s3 = 0;
+	walk_launch_centers(c, w, spec_inputs(sp, nobase), "k_wk_centers_Z");
+	HIPCHK(hipGetLastError());
+	*ready = true;
+	return 0;
+}
+
+/* launch_expect(alo, ahi) / launch_probe(grid) / launch_at(): the ploidy's kernels.  *done = false: nothing is changed (qq restored),
+ * the caller takes its other paths.  pro_done: the prologue of this sweep ran ahead (c->zq_pro_ready: what it found). */
+template <class LE, class LP, class LA>
+static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done, LE launch_expect, LP launch_probe, LA launch_at, bool second, bool *again, bool pro_done)
+{
+	*done = false;
+	*again = false;
+	if (!sp) return 0;
+	bool ready = pro_done && c->zq_pro_ready;
+	if (!pro_done && spec_ZQ_prologue(c, sp, launch_expect, second, &ready)) return 1;
+	if (!ready) return 0;
+	const int N = sp->N, K = sp->K;
+	WalkRun &w = sp->walk;
+	const WalkInputs in = spec_inputs(sp, base);
 	const int nseg = (int)w.plan.seg.size();
-	walk_launch_centers(c, w, in, "k_wk_centers_Z");
 	for (int s = 0; s < nseg; s++) {
 		walk_launch_tables(c, w, in, s, "k_wk_table_Z");
 		walk_launch_walk(c, w, in, s, 0, 0, "k_wk_walk_Z");
@@ -416,25 +449,33 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 	for (int r = 0; r < sp->rounds; r++) round();
 	finish(); /* (does nothing if the trajectory still holds uncertain bytes) */
 	HIPCHK(hipGetLastError());
-	struct { unsigned done, fail; unsigned long long total; } hr;
-	WkState hs;
-	SpecDev hd;
-	unsigned err[4] = {0, 0, 0, 0};
-	HIPCHK(hipMemcpyAsync(&hr, &sp->d_rs.get()->done, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(&hs, w.d_st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(&hd, sp->d_dev, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(err, c->d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	for (int extra = 0; extra < 12 && !hs.fail && !hd.overflow && hd.nlist != 0u; extra++) { /* not settled yet: round by round, looking each time */
+	MailZQ *m = mail_slot<MailZQ>(c, MAIL_ZQ);
+	auto look = [&]() -> int { /* the four answers into the look's slot, its event behind them */
+		HIPCHK(hipMemcpyAsync(&m->r, &sp->d_rs.get()->done, sizeof(m->r), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(&m->st, w.d_st, sizeof(m->st), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(&m->dev, sp->d_dev, sizeof(m->dev), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(m->err, c->d_err, sizeof(m->err), hipMemcpyDeviceToHost, c->stream));
+		return look_record(c, AH_LOOK_ZQ);
+	};
+	if (look()) return 1;
+	/* launch-ahead: if the blind rounds settled it, Z is final behind k_zq_at and cal_lkh's sweep (it does not read alpha) may as well run now */
+	bool lkh_early = false;
+	if (c->la_on && lkh_sweep_is_generic(c)) {
+		if (launch_lkh_sweep(c)) return 1;
+		lkh_early = true;
+	}
+	if (look_wait(c, AH_LOOK_ZQ)) return 1;
+	for (int extra = 0; extra < 12 && !m->st.fail && !m->dev.overflow && m->dev.nlist != 0u; extra++) { /* not settled yet: round by round, looking each time */
+		lkh_early = false; /* (it saw a Z that k_zq_at had not written) */
 		round();
 		finish();
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(&hr, &sp->d_rs.get()->done, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipMemcpyAsync(&hs, w.d_st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipMemcpyAsync(&hd, sp->d_dev, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipMemcpyAsync(err, c->d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
+		if (look() || look_wait(c, AH_LOOK_ZQ)) return 1;
 	}
+	const auto hr = m->r;
+	const WkState hs = m->st;
+	const SpecDev hd = m->dev;
+	unsigned err[4] = {m->err[0], m->err[1], m->err[2], m->err[3]};
 	sp->last_probes = hd.nprobes;
 	sp->last_rounds = hd.rounds;
 	sp->last_fail = hs.fail | (hd.overflow ? 16u : 0u) | ((err[0] & sp->err_bit) ? 32u : 0u) | (hd.nlist ? 64u : 0u);
@@ -464,18 +505,19 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 	sp->done++;
 	host_advance(c, hr.total);
 	c->h_qq = false;
+	if (lkh_early) ahead_set(&c->ah, AH_LKH);
 	*done = true;
 	return 0;
 }
 
 template <class LE, class LP, class LA>
-static int spec_update_ZQ_with(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done, LE launch_expect, LP launch_probe, LA launch_at)
+static int spec_update_ZQ_with(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done, LE launch_expect, LP launch_probe, LA launch_at, bool pro_done = false)
 {
 	bool again = false;
-	if (spec_update_ZQ_once(c, sp, base, done, launch_expect, launch_probe, launch_at, false, &again)) return 1;
+	if (spec_update_ZQ_once(c, sp, base, done, launch_expect, launch_probe, launch_at, false, &again, pro_done)) return 1;
 	if (!again) return 0;
 	sp->retried++;
-	return spec_update_ZQ_once(c, sp, base, done, launch_expect, launch_probe, launch_at, true, &again);
+	return spec_update_ZQ_once(c, sp, base, done, launch_expect, launch_probe, launch_at, true, &again, false);
 }
 
 template <int KMAX>
@@ -499,11 +541,24 @@ static void spec_launch_at(isg_ctx *c, SpecCtx *sp, isg_wh base)
 {
 	hipLaunchKernelGGL((k_zq_at<256, KMAX>), dim3(c->cfg.N), dim3(256), 0, c->stream, c->d, base, c->alpha, (const ResolveState *)sp->d_rs, (const unsigned long long *)sp->d_offs);
 }
-static int spec_update_ZQ(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done)
+static int spec_update_ZQ(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done, bool pro_done)
 {
 	const int K = c->cfg.K;
 	return spec_update_ZQ_with(c, sp, base, done,
 				   [&](float *alo, float *ahi) { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_expect<decltype(km)::value>(c, sp, alo, ahi); }); },
 				   [&](int grid) { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_probe<decltype(km)::value>(c, sp, base, grid); }); },
-				   [&]() { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_at<decltype(km)::value>(c, sp, base); }); });
+				   [&]() { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_at<decltype(km)::value>(c, sp, base); }); }, pro_done);
+}
+/* launch-ahead behind update_G's look (isg_iteration, diploid replay chains): the coming sweep's prologue, enqueued before the stream position
+ * of update_ZQ is known.  isg_update_ZQ takes AH_EXPECT and starts at the tables. */
+static int spec_ZQ_prologue_ahead(isg_ctx *c, SpecCtx *sp)
+{
+	const int K = c->cfg.K;
+	c->d.tape = nullptr; /* (as isg_update_ZQ leaves the view before it comes here) */
+	c->d.tape_len = 0;
+	bool ready = false;
+	if (spec_ZQ_prologue(c, sp, [&](float *alo, float *ahi) { kdispatch(KL_ZQ(), K, [&](auto km) { spec_launch_expect<decltype(km)::value>(c, sp, alo, ahi); }); }, false, &ready)) return 1;
+	c->zq_pro_ready = ready;
+	ahead_set(&c->ah, AH_EXPECT);
+	return 0;
 }

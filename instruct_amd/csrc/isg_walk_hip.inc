@@ -250,6 +250,7 @@ struct PDevCtx {
 	DevBuf<float> d_tapef;   /* the run's uniforms as floats */
 	unsigned long long tape_len = 0;
 	bool usable = false;
+	int test_abort = 0; /* INSTRUCT_P_TEST_ABORT=n: the n-th device sweep is treated as lost (tests) */
 	long sweeps = 0, fallbacks = 0, retried = 0; /* retried: sweeps whose tables were built a second time, with wider windows, after a missed one */
 };
 
@@ -354,6 +355,7 @@ static int pdev_create(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const 
 	if (p->G < 1) { delete p; return 0; }
 	p->walk.seg_groups = (int)env_int(getenv("INSTRUCT_WALK_SEG"), 12800, 64, INT_MAX); /* (config 3's 25000 groups: two segments, measured best of 4096 .. 25600; config 5 does not care) */
 	p->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), p->walk.kwin, 1.0);
+	p->test_abort = (int)env_int(getenv("INSTRUCT_P_TEST_ABORT"), 0);
 	*out = p; /* the context owns it from here on, whatever fails below (usable only at the end) */
 	HIPCHK(p->d_gam0.alloc((size_t)p->G + 1));
 	HIPCHK(p->d_gidx.alloc(p->NG));
@@ -368,8 +370,25 @@ static int pdev_create(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const 
 	return 0;
 }
 
-/* counts are in d.cnt (k_count has been launched).  *done = false: nothing was consumed, the caller runs the host loop. */
-static int pdev_update_P_once(isg_ctx *c, PDevCtx *p, bool *done, bool second, bool *again)
+/* the counts in d.cnt gathered into stream order and scanned into the gammas' minimal positions (no stream position goes in) */
+static void pdev_launch_prep(isg_ctx *c, PDevCtx *p)
+{
+	const unsigned nchunk = (unsigned)((p->NG + 1023) / 1024) + 1u; /* (+ 1: gpos[NG] when NG is a multiple of 1024) */
+	prof_begin(c);
+	hipLaunchKernelGGL(k_pd_gather, dim3(nchunk), dim3(256), 0, c->stream, (const int *)c->d.cnt, (const int *)p->d_gidx, p->NG, p->d_gcnt, p->d_part);
+	hipLaunchKernelGGL(k_pd_scan, dim3(nchunk), dim3(256), 0, c->stream, (const int *)p->d_gcnt, p->NG, (const unsigned *)p->d_part, p->d_gpos);
+	prof_end(c, "k_pd_prep");
+}
+/* what update_P's look brings back (the mailbox's slot MAIL_P) */
+struct MailP {
+	WkState st;
+	unsigned long long tail[2]; /* minimal consumption of the run; rejected attempts in all */
+};
+static_assert(sizeof(MailP) <= MAIL_G - MAIL_P, "update_P's slot of the mailbox");
+
+/* counts are in d.cnt (k_count has been launched; prepped: k_pd_gather and k_pd_scan too, behind update_alpha's look).  *done = false: nothing
+ * was consumed, the caller runs the host loop. */
+static int pdev_update_P_once(isg_ctx *c, PDevCtx *p, bool *done, bool second, bool *again, bool prepped)
 {
 	*done = false;
 	*again = false;
@@ -379,13 +398,7 @@ static int pdev_update_P_once(isg_ctx *c, PDevCtx *p, bool *done, bool second, b
 	if (!ok) { p->usable = false; return 0; }
 	WalkRun &w = p->walk;
 	HIPCHK(hipMemsetAsync(w.d_st, 0, sizeof(WkState), c->stream));
-	prof_begin(c);
-	{
-		const unsigned nchunk = (unsigned)((p->NG + 1023) / 1024) + 1u; /* (+ 1: gpos[NG] when NG is a multiple of 1024) */
-		hipLaunchKernelGGL(k_pd_gather, dim3(nchunk), dim3(256), 0, c->stream, (const int *)c->d.cnt, (const int *)p->d_gidx, p->NG, p->d_gcnt, p->d_part);
-		hipLaunchKernelGGL(k_pd_scan, dim3(nchunk), dim3(256), 0, c->stream, (const int *)p->d_gcnt, p->NG, (const unsigned *)p->d_part, p->d_gpos);
-	}
-	prof_end(c, "k_pd_prep");
+	if (!prepped) pdev_launch_prep(c, p);
 	/* the run's stretch of the stream as floats: at most 2 NG uniforms if nothing is rejected, about half an attempt per gamma on top */
 	prof_begin(c);
 	hipLaunchKernelGGL(k_tapef, dim3((unsigned)((p->tape_len + 2047) / 2048)), dim3(256), 0, c->stream, c->d.tab, c->rng, (unsigned long long)p->tape_len, p->d_tapef);
@@ -403,13 +416,21 @@ static int pdev_update_P_once(isg_ctx *c, PDevCtx *p, bool *done, bool second, b
 			   (const unsigned long long *)p->d_gpos, (const unsigned long long *)w.d_T, p->G, w.d_st);
 	prof_end(c, "k_pdirich_at");
 	HIPCHK(hipGetLastError());
-	WkState hs;
-	unsigned long long tail[2] = {0, 0}; /* minimal consumption of the run; rejected attempts in all */
-	HIPCHK(hipMemcpyAsync(&hs, w.d_st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(&tail[0], p->d_gpos + p->NG, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(&tail[1], w.d_T + p->G, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
+	MailP *m = mail_slot<MailP>(c, MAIL_P);
+	HIPCHK(hipMemcpyAsync(&m->st, w.d_st, sizeof(m->st), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(&m->tail[0], p->d_gpos + p->NG, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(&m->tail[1], w.d_T + p->G, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	if (look_record(c, AH_LOOK_P)) return 1;
+	if (c->la_on) { /* launch-ahead: freq is final if the look says so (if not, it is rewritten and its copies are made again) */
+		if (refresh_freqf(c)) return 1;
+		ahead_set(&c->ah, AH_FREQF);
+	}
+	if (look_wait(c, AH_LOOK_P)) return 1;
+	WkState hs = m->st;
+	const unsigned long long tail[2] = {m->tail[0], m->tail[1]};
 	walk_adapt(w, hs);
+	if (p->test_abort > 0 && --p->test_abort == 0) hs.fail |= 8u; /* (tests: as if k_pdirich_at's check had failed; the host loop redraws all of freq) */
+	if (hs.fail) ahead_wrote_freq(&c->ah);
 	if (!second && hs.fail == 1u) { /* only a window was missed (nothing has been drawn: k_pdirich_at does not start then): once more with the wider windows */
 		*again = true;
 		return 0;
@@ -423,11 +444,11 @@ static int pdev_update_P_once(isg_ctx *c, PDevCtx *p, bool *done, bool second, b
 	*done = true;
 	return 0;
 }
-static int pdev_update_P(isg_ctx *c, PDevCtx *p, bool *done)
+static int pdev_update_P(isg_ctx *c, PDevCtx *p, bool *done, bool prepped = false)
 {
 	bool again = false;
-	if (pdev_update_P_once(c, p, done, false, &again)) return 1;
+	if (pdev_update_P_once(c, p, done, false, &again, prepped)) return 1;
 	if (!again) return 0;
 	p->retried++;
-	return pdev_update_P_once(c, p, done, true, &again);
+	return pdev_update_P_once(c, p, done, true, &again, false);
 }
