@@ -154,6 +154,17 @@ class OrcChain:
     def indvlkh(self): return _view(self.lib.orc_indvlkh(self.h), (self.N,), np.float64)
     def alpha(self): return self.lib.orc_alpha(self.h)
     def set_alpha(self, a): self.lib.orc_set_alpha(self.h, a)
+
+    # the state setters write through the views above (the oracle keeps nothing cached beside them)
+    def set_z(self, z):
+        """z int [N][L][P]; entries at missing loci are not written (z() masks them anyway)"""
+        z = np.asarray(z, dtype=np.int32).reshape(self.N, self.L, self.P)
+        raw = self.z_raw()
+        raw[...] = np.where(self.valid()[:, :, None] != 0, z, raw)
+
+    def set_qq(self, q): self.qq()[...] = np.asarray(q, dtype=np.float64).reshape(self.N, self.K)
+    def set_generation(self, g): self.generation()[...] = np.asarray(g, dtype=np.int32).reshape(self.N)
+    def set_self_rates(self, s): self.self_rates()[...] = np.asarray(s, dtype=np.float64).reshape(-1)
     def totallkh(self): return self.lib.orc_totallkh(self.h)
     def error(self): return self.lib.orc_error(self.h)
 
