@@ -19,6 +19,7 @@
 #define PT_LOG(x) isg_log(x)
 #define PT_EXP(x) isg_exp(x)
 #include "isg_poly_tables.h"
+#include "isg_pgroups.h"
 #undef PT_NAME
 #undef PT_LOG
 #undef PT_EXP
@@ -42,6 +43,8 @@ struct PolyDev {
 	int *cnt;      /* [L][Amax][K] */
 	/* allotetraploid (-ap 0): copies 0, 1 of a genotype belong to the first subgenome (freq, cnt), copies 2, 3 to the second */
 	int allo;
+	int allo_pref; /* the allotetraploid genotype draw decides in single precision first (INSTRUCT_ALLO_PREFILTER=0: not): freqf is then followed
+	                * by the same copy of freq2, at freqf + Lp Amax KPF.  (Here, where the struct had padding: its size and offsets stay.) */
 	double *freq2; /* [L][Amax][KP]  UPMCMC.freq2 (update_P_allo, poly_geno.c:441-518) */
 	int *cnt2;     /* [L][Amax][K] */
 	int *cntmix2;  /* the second subgenome's copies of mixed-assignment loci */
@@ -55,7 +58,7 @@ struct PolyDev {
 	const isg_wh_tables *tab;
 	unsigned *err;
 	double log4, log6; /* isg_log(4), isg_log(6): the same bits as evaluating them per locus (poly_geno.c:880-882) */
-	const float *freqf; /* [L][Amax][KPF] single precision copy of freq (pre-filters) */
+	const float *freqf; /* [L][Amax][KPF] single precision copy of freq (pre-filters); allo_pref: followed by freq2's at freqf + Lp Amax KPF */
 	int KPF;
 	/* cal_lkd's tables, LOCUS INNERMOST (its lanes take consecutive loci: the lanes that need the same row read one contiguous stretch of it; in the
 	 * [locus][...] layouts every lane's 4 or 8 bytes cost a line of their own), rebuilt before cal_lkd reads them (k4_logfreq):
@@ -68,13 +71,13 @@ struct PolyDev {
 struct PolyCtx {
 	PolyDev p; /* a view of the buffers below (freqf, tab and err: of the context's) */
 	DevBuf<uint8_t> obs, geno, z;
-	DevBuf<int> nvalid, lclass, gidoff, cnt, cnt2, cntmix2, qqnum, ccnt;
+	DevBuf<int> nvalid, lclass, gidoff, cnt, cntmix2, qqnum, ccnt; /* allotetraploid: cnt holds cnt2 behind it, freq holds freq2 (isg_pgroups.h) */
 	DevBuf<unsigned> rankwave;
 	DevBuf<unsigned long long> ambwave, accbuf;
 	DevBuf<short> gidmap;
 	std::vector<DevBuf<int>> dlists; /* the classes' genotype lists: what the device copies of isg_polyclass point to */
 	DevBuf<isg_polyclass> pc;
-	DevBuf<double> freq, lfreq, freq2, lfreq2, qq, indvlkh;
+	DevBuf<double> freq, lfreq, lfreq2, qq, indvlkh;
 	DevBuf<float> exfreq, genofreq, genofreqT, tabtmp;
 	std::vector<int> classes;            /* distinct allele counts, ascending */
 	std::vector<std::vector<int>> lists; /* genotype lists per class */
@@ -91,6 +94,48 @@ struct PolyCtx {
 	hvec<int> cnt2_h;
 	std::vector<float> tab_h;
 };
+
+/* the single precision copy of freq2 behind freqf's (the allotetraploid genotype draw's pre-decision) */
+__global__ void k4_freq2f(PolyDev p)
+{
+	const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const size_t rows = (size_t)p.L * p.Amax;
+	if (id >= rows * p.KPF) return;
+	const size_t r = id / p.KPF;
+	const int m = (int)(id - r * p.KPF);
+	((float *)p.freqf)[(size_t)p.Lp * p.Amax * p.KPF + id] = (m < p.K) ? (float)p.freq2[r * p.KP + m] : 0.f;
+}
+
+/* pdev_create (isg_walk_hip.inc) for the allotetraploid chain: the group list of update_P_allo (pgroups_build, isg_pgroups.h: two Dirichlets per
+ * (k, j), the second's counts at cnt + sub_stride), twice the gammas, tape and segments; everything else of the engine is shared.  No context
+ * (*out stays null: the host loop draws) with INSTRUCT_P_DEVICE=0 or more alleles at a locus than a group holds; a plan that does not fit the
+ * engine (more than WK_MAXSEG segments) clears `usable` at the first sweep (pdev_update_P_once). */
+static int pdev_create_allo(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const int *allelenum, long long sub_stride)
+{
+	*out = nullptr;
+	if (!env_flag(getenv("INSTRUCT_P_DEVICE"), true)) return 0;
+	PGroups pg;
+	if (!pgroups_build(pg, L, K, Amax, allelenum, 0, 2, sub_stride, WK_NGMAX) || pg.gam0.size() < 2) return 0;
+	PDevCtx *p = new PDevCtx();
+	p->gam0_h = pg.gam0;
+	p->G = (int)pg.gam0.size() - 1;
+	p->NG = (int)pg.gidx.size();
+	p->walk.seg_groups = (int)env_int(getenv("INSTRUCT_WALK_SEG"), 12800, 64, INT_MAX);
+	p->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), p->walk.kwin, 1.0);
+	p->test_abort = (int)env_int(getenv("INSTRUCT_P_TEST_ABORT"), 0);
+	*out = p; /* the context owns it from here on, whatever fails below (usable only at the end) */
+	HIPCHK(p->d_gam0.alloc((size_t)p->G + 1));
+	HIPCHK(p->d_gidx.alloc(p->NG));
+	HIPCHK(p->d_gcnt.alloc(p->NG));
+	HIPCHK(p->d_gpos.alloc((size_t)p->NG + 1));
+	HIPCHK(p->d_part.alloc((size_t)(p->NG + 1023) / 1024 + 2));
+	p->tape_len = 2ull * (unsigned long long)p->NG + (unsigned long long)(1.7 * p->NG) + (unsigned long long)(12.0 * sqrt((double)p->NG)) + 8192ull;
+	HIPCHK(p->d_tapef.alloc(p->tape_len));
+	HIPCHK(hipMemcpy(p->d_gam0, p->gam0_h.data(), sizeof(int) * (p->G + 1), hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(p->d_gidx, pg.gidx.data(), sizeof(int) * p->NG, hipMemcpyHostToDevice));
+	p->usable = true;
+	return 0;
+}
 
 /* ---- exact accumulators in global memory: 4 x 32-bit limbs in 64-bit words + flags ---- */
 __device__ __forceinline__ void acc_global_add(unsigned long long *slot, const isg_acc &a)
@@ -164,9 +209,14 @@ __device__ __forceinline__ unsigned allo_pattern(int naid, int cand)
 #undef AP
 	return naid == 2 ? t2[cand] : naid == 3 ? t3[cand] : t4[cand];
 }
+#ifdef ISG_DIAG_ALLO_PREFILTER /* diagnostic builds only: draws of update_geno and how many of them the double precision path redid */
+__device__ unsigned long long isg_diag_allo_draws[2];
+#endif
+__device__ __forceinline__ float allo_sel4(const float (&v)[4], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3]; }
 /* initial_geno (uniform over the candidates, choose_unif poly_geno.c:840-852) and update_geno with choose_two / tri /
  * tetra_allo (poly_geno.c:962-1215) for -ap 0: one uniform per locus with two or more observed alleles */
-__device__ __forceinline__ void geno_one_allo(const PolyDev &p, const isg_wh &base, int init, const double *tape, int i, int j)
+template <int KMAX>
+__device__ __forceinline__ void geno_one_allo(const PolyDev &p, const isg_wh &base, int init, const double *tape, int i, int j, const float (&qf)[KMAX])
 {
 	const size_t id = (size_t)i * p.Lp + j;
 	unsigned o[4] = {0xff, 0xff, 0xff, 0xff};
@@ -192,11 +242,91 @@ __device__ __forceinline__ void geno_one_allo(const PolyDev &p, const isg_wh &ba
 		}
 		const int nc = naid == 2 ? 7 : naid == 3 ? 12 : 6;
 		double cum[12];
+		int pick = -1; /* decided by the single precision pre-decision below, else by the double precision path */
 		if (init) {
 			for (int a = 0; a < nc; a++) cum[a] = (double)(a + 1) / (double)nc;
 		} else {
 			const uint8_t *zz = p.z + id * 4;
 			const int n = p.pc[p.lclass[j]].n;
+			/*
+			 * Single precision pre-decision (as geno_one's, for 7, 12 or 6 candidates).  The weights are w_a = exp(t_a - t_0), the running sums
+			 * c_m = w_0 + .. + w_m, and the draw picks #{m < nc - 1 : c_m / tot < x} (isg_bucket: the LAST i with c_{i-1} < x tot <= c_i, 0 if
+			 * none; the c_m do not decrease, so that is the count).  With u = 2^-24, K clusters and M = max |log| that enters:
+			 *   f   K products of two rounded inputs and K - 1 additions of positive terms       relative (K + 2) u
+			 *   l   v_log_f32 (1 ulp of log2 f), times the rounded ln 2                           absolute (K + 2) u + 4 M u
+			 *   t   a constant and four logs, four additions of partial sums <= 4 M + 0.7         absolute (4 K + 11 + 32 M) u
+			 *   d   t_a - t_0, |d| <= 8 M + 1.4, one rounding                                     absolute (8 K + 24 + 72 M) u
+			 *   w   d times the rounded log2 e (2 u |d|), v_exp_f32 (1 ulp = 2 u)                  relative e = (8 K + 29 + 88 M) u
+			 * (same-cluster loci read t from the float table the double path reads too: only the last two rows apply, e covers them with M = max |t|).
+			 * c_m / tot = A / (A + B) with A and B sums of weights, each within a factor 1 +- e: it moves by at most 2 e r (1 - r) <= e / 2; the
+			 * up to 11 float additions of each sum and x tot (x rounded, one product) add 24 u.  The band is twice that first-order bound,
+			 * e + 48 u = (8 K + 77 + 88 M) u of tot around every one of the nc - 1 thresholds: 4e-5 for K = 10 and frequencies around 0.1.
+			 * M <= 60 is required (f >= 9e-27: products flushed to zero, < 1.2e-38 each, stay below u f; e < 4e-4, so first order holds);
+			 * beyond it, inside a band, or with tot not finite (overflow, NaN) the double precision path below decides.
+			 */
+			if (p.allo_pref) {
+				const float *freq2f = p.freqf + (size_t)p.Lp * p.Amax * p.KPF;
+				const bool samez_f = (zz[0] == zz[1] && zz[0] == zz[2] && zz[0] == zz[3]);
+				float l1f[4] = {0.f, 0.f, 0.f, 0.f}, l2f[4] = {0.f, 0.f, 0.f, 0.f}, lmax = 0.f;
+				const float *tbf = p.genofreq + ((size_t)zz[0] * p.L + j) * p.GS;
+				if (!samez_f) {
+#pragma unroll
+					for (int a = 0; a < 4; a++) {
+						if (a >= naid) continue;
+						const size_t r = ((size_t)j * p.Amax + o[a]) * p.KPF; /* whole rows with 16-byte loads (zero padded to KPF = K up to 4) */
+						const float4 *R1 = (const float4 *)(p.freqf + r), *R2 = (const float4 *)(freq2f + r);
+						float f1 = 0.f, f2 = 0.f;
+#pragma unroll
+						for (int b = 0; b < KMAX / 4; b++) {
+							if (4 * b >= p.KPF) continue;
+							const float4 r1 = R1[b], r2 = R2[b];
+							f1 += qf[4 * b] * r1.x + qf[4 * b + 1] * r1.y + qf[4 * b + 2] * r1.z + qf[4 * b + 3] * r1.w;
+							f2 += qf[4 * b] * r2.x + qf[4 * b + 1] * r2.y + qf[4 * b + 2] * r2.z + qf[4 * b + 3] * r2.w;
+						}
+						l1f[a] = __builtin_amdgcn_logf(f1) * 0.693147180559945f;
+						l2f[a] = __builtin_amdgcn_logf(f2) * 0.693147180559945f;
+						lmax = __builtin_fmaxf(lmax, __builtin_fmaxf(__builtin_fabsf(l1f[a]), __builtin_fabsf(l2f[a])));
+					}
+				}
+				float cf[12], t0 = 0.f;
+#pragma unroll
+				for (int a = 0; a < 12; a++) {
+					cf[a] = 0.f;
+					if (a >= nc) continue;
+					const unsigned pt = allo_pattern(naid, a);
+					const int p0 = pt & 3, p1 = (pt >> 2) & 3, p2 = (pt >> 4) & 3, p3 = (pt >> 6) & 3;
+					float t;
+					if (samez_f) {
+						t = tbf[isg_allo_row(n, (int)o[p0], (int)o[p1], (int)o[p2], (int)o[p3])];
+						lmax = __builtin_fmaxf(lmax, __builtin_fabsf(t));
+					} else {
+						t = (p0 != p1 && p2 != p3 && naid < 4) ? 0.693147180559945f + allo_sel4(l1f, p0) : allo_sel4(l1f, p0);
+						t += allo_sel4(l1f, p1);
+						t += allo_sel4(l2f, p2);
+						t += allo_sel4(l2f, p3);
+					}
+					if (a == 0) { t0 = t; cf[0] = 1.f; }
+					else cf[a] = cf[a - 1] + __builtin_amdgcn_exp2f((t - t0) * 1.44269504f);
+				}
+				float tot = cf[0];
+#pragma unroll
+				for (int a = 1; a < 12; a++) tot = (a < nc) ? cf[a] : tot;
+				const float pf = (float)x * tot, band = ((float)(8 * p.K + 77) + 88.f * lmax) * 5.9604645e-8f * tot;
+				bool clear = (tot < 1e30f) && (lmax <= 60.f);
+				int below = 0;
+#pragma unroll
+				for (int m = 0; m < 11; m++) {
+					if (m >= nc - 1) continue;
+					clear = clear && (__builtin_fabsf(pf - cf[m]) > band);
+					below += (pf > cf[m]) ? 1 : 0;
+				}
+				if (clear) pick = below;
+			}
+#ifdef ISG_DIAG_ALLO_PREFILTER
+			atomicAdd(&isg_diag_allo_draws[0], 1ull);
+			if (pick < 0) atomicAdd(&isg_diag_allo_draws[1], 1ull);
+#endif
+			if (pick < 0) {
 			double tmp[12];
 			if (zz[0] == zz[1] && zz[0] == zz[2] && zz[0] == zz[3]) {
 				const float *tb = p.genofreq + ((size_t)zz[0] * p.L + j) * p.GS;
@@ -233,8 +363,10 @@ __device__ __forceinline__ void geno_one_allo(const PolyDev &p, const isg_wh &ba
 			const double tm = tmp[0];
 			cum[0] = 1.0; /* exp(tmp[0] - tmp[0]): isg_exp(0) == 1 exactly (checked at context creation) */
 			for (int a = 1; a < nc; a++) cum[a] = isg_exp(tmp[a] - tm) + cum[a - 1];
+			}
 		}
-		const unsigned pt = allo_pattern(naid, isg_bucket(x, cum, nc));
+		if (pick < 0) pick = isg_bucket(x, cum, nc);
+		const unsigned pt = allo_pattern(naid, pick);
 		g[0] = o[pt & 3]; g[1] = o[(pt >> 2) & 3]; g[2] = o[(pt >> 4) & 3]; g[3] = o[(pt >> 6) & 3];
 	}
 	*(unsigned *)(p.geno + id * 4) = g[0] | (g[1] << 8) | (g[2] << 8 * 2) | (g[3] << 8 * 3);
@@ -410,10 +542,21 @@ __global__ void __launch_bounds__(256) k4_geno(PolyDev p, isg_wh base, int init,
 		float qf[KMAX]; /* the individual's admixture row in single precision (pre-filter only) */
 #pragma unroll
 		for (int m = 0; m < KMAX; m++) qf[m] = (m < p.K && !init) ? (float)p.qq[(size_t)i * p.K + m] : 0.f;
-		if (ALLO) geno_one_allo(p, base, init, tape, i, j);
+		if (ALLO) geno_one_allo<KMAX>(p, base, init, tape, i, j, qf);
 		else geno_one<KMAX, WIDE>(p, base, init, tape, i, j, qf);
 	}
 }
+
+#ifdef ISG_DIAG_ALLO_PREFILTER
+extern "C" int isg_diag_allo_prefilter(long out[2]) /* {draws of update_geno, of them redone in double precision} since the library was loaded */
+{
+	unsigned long long v[2] = {0, 0};
+	HIPCHK(hipMemcpyFromSymbol(v, HIP_SYMBOL(isg_diag_allo_draws), sizeof(v)));
+	out[0] = (long)v[0];
+	out[1] = (long)v[1];
+	return 0;
+}
+#endif
 
 /*
  * THE sweep over (genotype, Z) of an iteration, shared by update_P_auto and update_S_POP:
@@ -1434,13 +1577,11 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 		cls[q].list = pc->dlists[q];
 	}
 	HIPCHK(pc->pc.upload(cls));
-	HIPCHK(pc->freq.alloc_zero(nfreq));
-	HIPCHK(pc->lfreq.alloc_zero(nfreq));
-	HIPCHK(pc->cnt.alloc_zero(ncnt));
+	HIPCHK(pc->freq.alloc_zero(allo ? 2 * nfreq : nfreq)); /* allotetraploid: freq2 and cnt2 follow freq and cnt, so that a count index beyond ncnt */
+	HIPCHK(pc->lfreq.alloc_zero(nfreq));                  /* names the second subgenome's count and frequency (isg_pgroups.h) */
+	HIPCHK(pc->cnt.alloc_zero(allo ? 2 * ncnt : ncnt));
 	if (allo) {
-		HIPCHK(pc->freq2.alloc_zero(nfreq));
 		HIPCHK(pc->lfreq2.alloc_zero(nfreq));
-		HIPCHK(pc->cnt2.alloc_zero(ncnt));
 		HIPCHK(pc->cntmix2.alloc_zero(ncnt));
 		pc->freq2_h.assign((size_t)K * L * Amax, 0.0);
 		pc->cnt2_h.assign((size_t)L * Amax * K, 0);
@@ -1460,13 +1601,15 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 	HIPCHK(pc->d_catcnt.alloc_zero(8));
 	p.obs = pc->obs; p.geno = pc->geno; p.z = pc->z; p.nvalid = pc->nvalid; p.rankwave = pc->rankwave; p.ambwave = pc->ambwave; p.lclass = pc->lclass;
 	p.gidmap = pc->gidmap; p.gidoff = pc->gidoff; p.pc = pc->pc; p.freq = pc->freq; p.lfreq = pc->lfreq; p.cnt = pc->cnt;
-	p.freq2 = pc->freq2; p.lfreq2 = pc->lfreq2; p.cnt2 = pc->cnt2; p.cntmix2 = pc->cntmix2;
+	p.freq2 = allo ? pc->freq + nfreq : nullptr; p.lfreq2 = pc->lfreq2; p.cnt2 = allo ? pc->cnt + ncnt : nullptr; p.cntmix2 = pc->cntmix2;
 	p.qq = pc->qq; p.qqnum = pc->qqnum; p.indvlkh = pc->indvlkh; p.exfreq = pc->exfreq; p.genofreq = pc->genofreq; p.genofreqT = pc->genofreqT;
 	p.tabtmp = pc->tabtmp; p.ccnt = pc->ccnt; p.accbuf = pc->accbuf;
 	pc->counts_valid = false;
 	pc->freq_host = true;
 	d.KPF = (K + 3) & ~3;
-	HIPCHK(c->d_freqf.alloc_zero((size_t)Lp * Amax * d.KPF));
+	/* the genotype draw's single precision pre-decision (geno_one_allo) reads freq2 in float too: its copy follows freq's */
+	p.allo_pref = (allo && env_flag(getenv("INSTRUCT_ALLO_PREFILTER"), true)) ? 1 : 0;
+	HIPCHK(c->d_freqf.alloc_zero((size_t)Lp * Amax * d.KPF * (p.allo_pref ? 2 : 1)));
 	p.freqf = d.freqf = c->d_freqf;
 	p.KPF = d.KPF;
 	{
@@ -1481,7 +1624,8 @@ static int poly_ctx_create(const isg_config *cfg, const int32_t *allelenum, cons
 		if (c->rs) c->rs->err_bit = 8u;
 	}
 	if (cfg->rng_sched == ISG_SCHED_REPLAY) {
-		if (!allo && pdev_create(c, &c->pdev, L, K, Amax, allelenum, 0)) return 1; /* update_P_auto has no allelenum > 1 test (poly_geno.c:426-434) */
+		/* neither update_P_auto (poly_geno.c:426-434) nor update_P_allo (:491-502) has an allelenum > 1 test; the latter draws two Dirichlets per (k, j) */
+		if (allo ? pdev_create_allo(c, &c->pdev, L, K, Amax, allelenum, (long long)ncnt) : pdev_create(c, &c->pdev, L, K, Amax, allelenum, 0)) return 1;
 		if (spec_create(c, &c->zspec, nvalid, 4)) return 1;
 		if (c->zspec) {
 			c->zspec->err_bit = 8u;
@@ -1605,6 +1749,12 @@ static void poly_launch_genfreq(isg_ctx *c, const float *self, int own)
 static int poly_after_draw(isg_ctx *c, bool on_host)
 {
 	if (refresh_freqf(c)) return 1;
+	if (c->poly->p.allo_pref) {
+		const size_t n = (size_t)c->poly->p.L * c->poly->p.Amax * c->poly->p.KPF;
+		prof_begin(c);
+		hipLaunchKernelGGL(k4_freq2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->poly->p);
+		prof_end(c, "k4_freq2f");
+	}
 	prof_begin(c);
 	poly_launch_exfreq(c);
 	prof_end(c, c->poly->wide ? "k4_exfreq_w" : "k4_exfreq");
@@ -1613,7 +1763,7 @@ static int poly_after_draw(isg_ctx *c, bool on_host)
 	return 0;
 }
 
-static int poly_update_P(isg_ctx *c) /* update_P_auto */
+static int poly_update_P(isg_ctx *c) /* update_P_auto / update_P_allo */
 {
 	PolyDev &p = c->poly->p;
 	const int L = p.L, K = p.K, A = p.Amax;
@@ -1625,12 +1775,12 @@ static int poly_update_P(isg_ctx *c) /* update_P_auto */
 		HIPCHK(hipGetLastError());
 		return poly_after_draw(c, false);
 	}
-	if (c->pdev && c->pdev->usable) { /* the Dirichlets' start positions resolved on the device, all of them drawn at once (isg_walk_hip.inc) */
+	if (c->pdev && c->pdev->usable) { /* the Dirichlets' start positions resolved on the device, all of them drawn at once (isg_walk_hip.inc); both variants */
 		bool done = false;
 		if (pdev_update_P(c, c->pdev, &done)) return 1;
 		if (done) return poly_after_draw(c, false);
 	}
-	/* the host loop; no allelenum > 1 test on this path (poly_geno.c:426-434) */
+	/* the host loop (both subgenomes from this stream position); no allelenum > 1 test on this path (poly_geno.c:426-434, 491-502) */
 	const HostPSecond second = {p.cnt2, c->poly->cnt2_h.data(), c->poly->freq2_h.data()};
 	if (host_update_P(c, HOSTP_REQUEST | HOSTP_DRAW, p.cnt, p.allo ? &second : nullptr, false)) return 1;
 	auto ht0 = std::chrono::steady_clock::now();

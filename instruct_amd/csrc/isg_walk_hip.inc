@@ -333,8 +333,8 @@ __global__ void __launch_bounds__(128) k_pdirich_at(DevView d, isg_wh base, cons
 }
 
 /* groups in the reference's order: for k < K, for j < L with allelenum[j] > min_alleles (mcmc.c:846-857 skips allelenum <= 1;
- * update_P_auto, poly_geno.c:426-434, does not), the alleles of (k, j); `sub` subgenomes per (k, j) (allotetraploid: 2, counts at
- * cnt and cnt + sub_stride) */
+ * update_P_auto, poly_geno.c:426-434, does not), the alleles of (k, j).  The allotetraploid chain's list -- two groups per (k, j), the second
+ * subgenome's counts at cnt + sub_stride -- comes from pgroups_build (isg_pgroups.h) through pdev_create_allo (isg_poly_hip.inc) */
 static int pdev_create(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const int *allelenum, int min_alleles)
 {
 	*out = nullptr;
