@@ -281,6 +281,44 @@ def test_replay_host_update_P_requested_ahead_bit_exact_vs_canonical_oracle(monk
     h.close()
 
 
+@pytest.mark.parametrize("shape", [(16, 3001, 2), (12, 300, 2)])
+def test_replay_host_update_P_request_is_dropped_when_stale_bit_exact_vs_canonical_oracle(shape, monkeypatch):
+    """INSTRUCT_P_DEVICE=0: every update_alpha leaves a request for the next update_P's counts and uniforms behind.  It must not be used
+    after a write of Z (set_z), after the stream has been moved without one (setseeds), and the request of an update_alpha that another
+    update_alpha followed is the older of two.  11940 gammas (the neighbouring test's shape): the tape comes from the device; 1200: the
+    host steps the generator itself and only the counts are requested."""
+    monkeypatch.setenv("INSTRUCT_P_DEVICE", "0")
+    N, L, K = shape
+    geno, an, mi = synth.code_diploid(synth.raw_alleles(N, L, K, 2, 2, 0.1, 29))
+    h, o, initd = _pair(geno, an, mi, K, capi.SCHED_REPLAY)
+    state = ["z", "qq", "qqnum", "generation", "alpha", "self_rates", "freq", "indvlkh", "totallkh", "seeds"]
+
+    def iteration(where):
+        h.iteration()
+        o.iteration()
+        _same(h, o, state, where)
+
+    h.chain_init(initd)
+    o.chain_init(initd)
+    iteration("first")   # a request is outstanding now
+    z = h.z()
+    z = np.where(z >= 0, K - 1 - z, z)
+    h.set_z(z)
+    o.set_z(z)
+    _same(h, o, state, "set_z")
+    iteration("after set_z")
+    h.setseeds(1, 2, 3)
+    o.setseeds(1, 2, 3)
+    _same(h, o, state, "setseeds")
+    iteration("after setseeds")
+    for sweep in ("update_P", "update_S_POP", "update_G", "update_ZQ", "update_alpha", "update_alpha", "cal_lkh", "update_P"):
+        getattr(h, sweep)()
+        getattr(o, sweep)()
+        _same(h, o, state, sweep)
+    assert o.error() == 0
+    h.close()
+
+
 @pytest.mark.parametrize("persist", ["1", "0"])
 @pytest.mark.parametrize("K", [1, 2, 3, 4, 6, 7, 8])
 def test_replay_block_resolver_every_K_bit_exact(K, persist, monkeypatch):
