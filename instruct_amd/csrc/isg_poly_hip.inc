@@ -122,6 +122,7 @@ static int pdev_create_allo(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, c
 	p->NG = (int)pg.gidx.size();
 	p->walk.seg_groups = (int)env_int(getenv("INSTRUCT_WALK_SEG"), 12800, 64, INT_MAX);
 	p->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), p->walk.kwin, 1.0);
+	walk_read_trim_env(p->walk);
 	p->test_abort = (int)env_int(getenv("INSTRUCT_P_TEST_ABORT"), 0);
 	*out = p; /* the context owns it from here on, whatever fails below (usable only at the end) */
 	HIPCHK(p->d_gam0.alloc((size_t)p->G + 1));

@@ -338,6 +338,7 @@ static int spec_create(isg_ctx *c, SpecCtx **out, const std::vector<int> &nvalid
 	sp->ksig = (float)env_double(getenv("INSTRUCT_ZQ_SPEC_KSIG"), sp->ksig, 1.0);
 	sp->walk.seg_groups = (int)env_int(getenv("INSTRUCT_ZQ_SPEC_SEG"), 16384, 64, INT_MAX);
 	sp->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), sp->walk.kwin, 1.0);
+	walk_read_trim_env(sp->walk);
 	sp->test_abort = (int)env_int(getenv("INSTRUCT_ZQ_SPEC_TEST_ABORT"), 0);
 	sp->list_cap = 6 * N + 1024;
 	*out = sp; /* the context owns it from here on, whatever fails below */

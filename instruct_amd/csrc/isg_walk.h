@@ -64,8 +64,9 @@
 #define WK_ATOMIC_ADD_F64(p, v) atomicAdd((p), (v))
 #define WK_LOG2F(x) __builtin_amdgcn_logf(x)
 #define WK_RCPF(x) __builtin_amdgcn_rcpf(x)
-/* bit `col` of a row: the 64 lanes of a wave hold 64 consecutive columns starting at a multiple of 64 (loops of stride
- * nthreads over a multiple of 64 columns): one ballot, two stores by lane 0, no atomics */
+/* bit `col` of a row: the 64 lanes of a wave hold 64 consecutive columns starting at a multiple of 32 (loops of stride
+ * nthreads from a multiple of 32; lanes beyond the loop's end vote 0 into a word nobody else writes): one ballot, two stores by
+ * lane 0, no atomics */
 #define WK_PUT_BIT(row, col, bit) do { const unsigned long long bm_ = __ballot(bit); if ((threadIdx.x & 63u) == 0u) { (row)[(col) >> 5] = (unsigned)bm_; (row)[((col) >> 5) + 1] = (unsigned)(bm_ >> 32); } } while (0)
 #else
 #include <math.h>
@@ -89,6 +90,8 @@ typedef struct {
 	int ein;                  /* entry offsets wlo .. wlo + ein - 1 are mapped (ein <= W) */
 	unsigned foff;            /* its map F1: ein 16-bit deltas at maps + foff */
 	unsigned long long toff;  /* its table: ng rows of W bytes at table + toff */
+	float tspread;            /* a row's reachable columns (wk_trim_range): their spread in rejections per sqrt(gamma); 0: every column is evaluated */
+	float tpred;              /* ... and the rejections predicted inside the block, scaled (wk_centers writes it next to wlo; below 0: every column) */
 } WkBlock;
 typedef struct {
 	int b0, nb;               /* first block, blocks */
@@ -365,6 +368,33 @@ ISG_HD size_t wk_table_lds_bytes(int W, int ngmax, int mode)
 	return sizeof(float) * wk_tape_floats(W) + sizeof(WkCoefI) * WK_NGMAX + sizeof(unsigned) * (1 + WK_AMBCAP) + sizeof(unsigned) * rows;
 }
 
+/*
+ * The columns a row of a block can be entered at.  All rows of a block are W columns wide -- its entry columns [0, ein) and room for the
+ * drift of ALL its gammas -- but the row behind `nbefore` of the block's `nin` gammas is only reached from
+ *     [pred - s, ein + pred + s),    pred = tpred nbefore / nin,    s = tspread sqrt(nbefore) + WK_TRIM_MARGIN
+ * (the block's predicted rejections in proportion; the spread the entry windows themselves are sized with).  Rounded outwards to multiples
+ * of 32 inside [0, W).  wk_table evaluates these columns only and writes WK_IRR elsewhere; wk_final tells a walk that stepped outside
+ * (a missed window) from one that met an irregular byte with the same function.  Returns 0, and the whole row, for a block that is not
+ * trimmed: tspread = 0 (the plan), tpred < 0 (wk_centers: the last block of a segment, a window clamped at offset 0).
+ */
+#define WK_TRIM_MARGIN 8
+ISG_HD int wk_trim_range(const WkBlock B, int nbefore, int nin, int *lo, int *hi)
+{
+	*lo = 0;
+	*hi = B.W;
+	if (!(B.tspread > 0.f) || !(B.tpred >= 0.f) || nin < 1 || nbefore < 0 || nbefore > nin) return 0;
+	const float pred = B.tpred * ((float)nbefore / (float)nin);
+	const float s = B.tspread * __builtin_sqrtf((float)nbefore) + (float)WK_TRIM_MARGIN;
+	const float l = __builtin_floorf(pred - s), h = __builtin_ceilf(pred + s) + (float)B.ein;
+	if (!(l < (float)B.W) || !(h > 0.f)) return 0; /* (NaN, or a prediction beyond the table: nothing to go by) */
+	const int li = l > 0.f ? ((int)l & ~31) : 0;
+	const int hi_ = h < (float)B.W ? (((int)h + 31) & ~31) : B.W;
+	if (li >= hi_) return 0;
+	*lo = li;
+	*hi = hi_ < B.W ? hi_ : B.W;
+	return 1;
+}
+
 /* one workgroup per group: wg = group - seg_g0; nthreads a multiple of 64 */
 ISG_HD void wk_table_body(const WkTableArgs A, int wg, int nthreads, unsigned char *lds)
 {
@@ -376,6 +406,10 @@ ISG_HD void wk_table_body(const WkTableArgs A, int wg, int nthreads, unsigned ch
 	const unsigned long long p0 = A.gpos[gm0];
 	const int span = (int)(A.gpos[gm0 + ng - 1] - p0);
 	const int ntape = 2 * Wp + span + 2;
+	int lo, hi; /* the columns this row is entered at: evaluated are [lo, hi + WK_PADC) */
+	(void)wk_trim_range(B, gm0 - A.gam0[B.g0], A.gam0[B.g0 + B.ng] - A.gam0[B.g0], &lo, &hi);
+	const int he = hi + WK_PADC;
+	const int tlo = 2 * lo, thi = 2 * he + span + 2; /* their stretch of the tape (thi <= ntape) */
 	float *tape = (float *)lds;
 	WkCoef *coef = (WkCoef *)(lds + sizeof(float) * wk_tape_floats(W));
 	WkCoefI *coefi = (WkCoefI *)coef; /* (interval mode) */
@@ -396,16 +430,16 @@ ISG_HD void wk_table_body(const WkTableArgs A, int wg, int nthreads, unsigned ch
 	WK_THREADS(t, nthreads) {
 		if (A.tape && s0 + (unsigned long long)ntape <= A.tape_len) { /* (the same for every thread) */
 			const float *src = A.tape + s0;
-			int i = t;
-			for (; i + 3 * nthreads < ntape; i += 4 * nthreads) { /* four loads in flight per thread */
+			int i = tlo + t;
+			for (; i + 3 * nthreads < thi; i += 4 * nthreads) { /* four loads in flight per thread */
 				const float a = src[i], b = src[i + nthreads], c = src[i + 2 * nthreads], d = src[i + 3 * nthreads];
 				tape[i] = a; tape[i + nthreads] = b; tape[i + 2 * nthreads] = c; tape[i + 3 * nthreads] = d;
 			}
-			for (; i < ntape; i += nthreads) tape[i] = src[i];
+			for (; i < thi; i += nthreads) tape[i] = src[i];
 		} else {
-			for (int i0 = t * 16; i0 < ntape; i0 += nthreads * 16) { /* 16 per skip-ahead */
+			for (int i0 = tlo + t * 16; i0 < thi; i0 += nthreads * 16) { /* 16 per skip-ahead */
 				isg_wh s = isg_wh_jump(A.tab, A.base, s0 + (unsigned long long)i0);
-				for (int k = 0; k < 16 && i0 + k < ntape; k++) {
+				for (int k = 0; k < 16 && i0 + k < thi; k++) {
 					isg_wh_step(&s);
 					/* interval mode: the bits are speculation anyway, the cheaper single precision evaluation (error < 1e-6) will do */
 					tape[i0 + k] = interval ? isg_wh_value_f32(&s) : (float)isg_wh_value(&s);
@@ -420,7 +454,7 @@ ISG_HD void wk_table_body(const WkTableArgs A, int wg, int nthreads, unsigned ch
 		}
 	}
 	WK_SYNC();
-	/* phase 1: the accept bit of every (gamma, column) */
+	/* phase 1: the accept bit of every (gamma, column the row can be entered at or reach from there) */
 	WK_THREADS(t, nthreads) {
 		for (int m = 0; m < ng; m++) {
 			const int om = (int)(A.gpos[gm0 + m] - p0);
@@ -428,7 +462,7 @@ ISG_HD void wk_table_body(const WkTableArgs A, int wg, int nthreads, unsigned ch
 			WkCoefI ki;
 			if (interval) { ki = coefi[m]; k0 = wk_coef(1.0); }
 			else { k0 = coef[m]; ki = wk_coef_interval(0.0, 0.0); }
-			for (int col = t; col < Wp; col += nthreads) {
+			for (int col = lo + t; col < he; col += nthreads) { /* (lo: a multiple of 32, as WK_PUT_BIT wants lane 0's column) */
 				const int o = om + 2 * col;
 				int acc, unc = 0, amb0;
 				if (!interval) {
@@ -471,6 +505,7 @@ ISG_HD void wk_table_body(const WkTableArgs A, int wg, int nthreads, unsigned ch
 		unsigned char *out = A.table + B.toff + (size_t)r * W;
 		const int nwv = Wp / 32;
 		for (int col = t; col < W; col += nthreads) {
+			if (col < lo || col >= hi) { out[col] = (unsigned char)WK_IRR; continue; } /* no walk enters the row here */
 			int X = col, bad = 0, unc = 0;
 			for (int m = 0; m < ng; m++) {
 				const int X1 = wk_nextset_flag(rows + m * nw, interval ? rows + (ng + m) * nw : (const unsigned *)0, nwv, X, &unc);
@@ -563,8 +598,11 @@ ISG_HD void wk_centers_body(WkCenterArgs A, int wg, int nthreads, unsigned char 
 			} else {
 				const int c = (int)(run * A.scale);
 				int lo = c - A.hw[A.seg.b0 + b];
-				if (lo < 0 && A.seg.g0 == 0) lo = 0; /* (later segments: a second walk may enter below the origin, hw[first block] > 0) */
+				const int clamped = (lo < 0 && A.seg.g0 == 0);
+				if (clamped) lo = 0; /* (later segments: a second walk may enter below the origin, hw[first block] > 0) */
 				A.blk[A.seg.b0 + b].wlo = lo;
+				/* what wk_trim_range goes by; the segment's last block (it may be any length) and a clamped window keep every column */
+				A.blk[A.seg.b0 + b].tpred = (clamped || b == A.seg.nb - 1) ? -1.0f : sum[b] * A.scale;
 			}
 		}
 	}
@@ -798,6 +836,11 @@ ISG_HD void wk_final_body(const WkWalkArgs A, int wg, int nthreads, unsigned cha
 				const int c = wk_byte_step(v, A.mode, A.strict, &why);
 				if (c < 0) break;
 				col += c;
+			}
+			if ((why & 2u) && r < B.ng) { /* an irregular byte, or a column wk_table left out: the walk has left the row's window */
+				const int gb = A.gam0[B.g0];
+				int lo, hi;
+				if (wk_trim_range(B, A.gam0[B.g0 + r] - gb, A.gam0[B.g0 + B.ng] - gb, &lo, &hi) && (col < lo || col >= hi)) why = (why & ~2u) | 1u;
 			}
 			if (why) {
 				WK_ATOMIC_OR(&A.st->fail, why);

@@ -87,19 +87,36 @@ struct WalkRun {
 	int seg_groups = 8192;
 	int plan_seg_groups = 0, plan_slack = 0; /* what the current plan was built for */
 	long runs = 0, fails = 0;
+	/* the tables' rows are evaluated at the columns a row can be entered at only (wk_trim_range); trim_k: their spread in sigma, 0 = the walk's kwin */
+	bool trim = true;
+	double trim_k = 0.0;
 };
+/* INSTRUCT_WALK_TRIM / INSTRUCT_WALK_TRIM_K, read where a run's context is created */
+static void walk_read_trim_env(WalkRun &w)
+{
+	w.trim = env_flag(getenv("INSTRUCT_WALK_TRIM"), true);
+	w.trim_k = env_double(getenv("INSTRUCT_WALK_TRIM_K"), 0.0, 0.0);
+}
+/* the spread the next plan trims its rows with: it widens with the windows after a miss (walk_adapt) */
+static double walk_trim_k(const WalkRun &w)
+{
+	if (!w.trim) return 0.0;
+	if (!(w.trim_k > 0.0)) return w.kwin;
+	return w.trim_k * (w.kwin0 > 0.0 ? w.kwin / w.kwin0 : 1.0);
+}
 
 /* (re)builds the plan for the current window statistics and makes the buffers fit; false: the run does not fit the engine */
 static int walk_prepare(isg_ctx *c, WalkRun &w, const int *gam0_h, int G, int mode, bool reuse, bool *ok, int entry_slack = 0)
 {
 	*ok = false;
+	const double trim_k = walk_trim_k(w);
 	if (w.plan_ok && w.mode == mode && w.plan.groups == G && w.plan.rho_hi == w.rho_hi && w.plan.sigma == w.sigma && w.plan.kwin == w.kwin && w.plan.reuse == reuse &&
-	    w.plan_seg_groups == w.seg_groups && w.plan_slack == entry_slack) { /* same statistics as last time: same plan (building one costs the host 0.1 ms at 25000 groups) */
+	    w.plan_seg_groups == w.seg_groups && w.plan_slack == entry_slack && w.plan.trim_k == trim_k) { /* same statistics as last time: same plan (building one costs the host 0.1 ms at 25000 groups) */
 		*ok = true;
 		return 0;
 	}
 	WkPlan np;
-	if (!wk_plan_build(np, gam0_h, G, w.rho_hi, w.sigma, w.kwin, w.seg_groups, reuse, mode, entry_slack)) { w.plan_ok = false; return 0; }
+	if (!wk_plan_build(np, gam0_h, G, w.rho_hi, w.sigma, w.kwin, w.seg_groups, reuse, mode, entry_slack, trim_k)) { w.plan_ok = false; return 0; }
 	w.plan_seg_groups = w.seg_groups;
 	w.plan_slack = entry_slack;
 	const bool same = w.plan_ok && np.blk.size() == w.plan.blk.size() && np.sup.size() == w.plan.sup.size() && np.seg.size() == w.plan.seg.size() &&
@@ -139,6 +156,7 @@ static int walk_prepare(isg_ctx *c, WalkRun &w, const int *gam0_h, int G, int mo
 		w.plan.sigma = np.sigma;
 		w.plan.kwin = np.kwin;
 		w.plan.rho_hi = np.rho_hi;
+		w.plan.trim_k = np.trim_k;
 	}
 	if (!w.attrs_set) {
 		HIPCHK(hipFuncSetAttribute((const void *)k_wk_table<WK_MODE_EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -355,6 +373,7 @@ static int pdev_create(isg_ctx *c, PDevCtx **out, int L, int K, int Amax, const 
 	if (p->G < 1) { delete p; return 0; }
 	p->walk.seg_groups = (int)env_int(getenv("INSTRUCT_WALK_SEG"), 12800, 64, INT_MAX); /* (config 3's 25000 groups: two segments, measured best of 4096 .. 25600; config 5 does not care) */
 	p->walk.kwin = env_double(getenv("INSTRUCT_WALK_K"), p->walk.kwin, 1.0);
+	walk_read_trim_env(p->walk);
 	p->test_abort = (int)env_int(getenv("INSTRUCT_P_TEST_ABORT"), 0);
 	*out = p; /* the context owns it from here on, whatever fails below (usable only at the end) */
 	HIPCHK(p->d_gam0.alloc((size_t)p->G + 1));

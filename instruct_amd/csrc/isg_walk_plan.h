@@ -21,6 +21,7 @@ struct WkPlan {
 	size_t lds_table = 0, lds_block = 0, lds_compose = 0, lds_top = 0;
 	int groups = 0, ngmax = 0;
 	double rho_hi = 0, sigma = 0, kwin = 0;
+	double trim_k = 0;        /* a row's reachable columns are taken +-trim_k sigma sqrt(gammas before it in its block) wide (0: rows are not trimmed) */
 	bool reuse = true;
 };
 
@@ -32,14 +33,16 @@ struct WkPlan {
  * false: the run does not fit the engine's limits (the caller uses its sequential path).
  */
 /* entry_slack (interval mode, segments after the first): a later walk over the same tables may enter a segment this far from where the
- * walk that built them did */
-static bool wk_plan_build(WkPlan &P, const int *gam0, int G, double rho_hi, double sigma, double kwin, int seg_groups, bool reuse, int mode, int entry_slack = 0)
+ * walk that built them did.  trim_k > 0: wk_table evaluates only the columns a row can be entered at (wk_trim_range); sizes and addresses
+ * are the same either way. */
+static bool wk_plan_build(WkPlan &P, const int *gam0, int G, double rho_hi, double sigma, double kwin, int seg_groups, bool reuse, int mode, int entry_slack = 0, double trim_k = 0.0)
 {
 	P = WkPlan();
 	P.groups = G;
 	P.rho_hi = rho_hi;
 	P.sigma = sigma;
 	P.kwin = kwin;
+	P.trim_k = trim_k > 0.0 ? trim_k : 0.0;
 	P.reuse = reuse;
 	if (G < 1) return false;
 	for (int g = 0; g < G; g++) {
@@ -90,6 +93,8 @@ static bool wk_plan_build(WkPlan &P, const int *gam0, int G, double rho_hi, doub
 				B.W = ((B.ein + grow) + 63) & ~63;
 				B.toff = toff;
 				B.foff = (unsigned)foff;
+				B.tspread = (float)(P.trim_k * sigma);
+				B.tpred = -1.0f; /* (wk_centers) */
 				toff += (size_t)B.ng * B.W;
 				foff += (size_t)WK_EIN8(B.ein);
 				if ((size_t)B.ng * B.W > WK_LDS_BUDGET) ok = false;
