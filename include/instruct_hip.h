@@ -100,7 +100,7 @@ int isg_set_z(isg_ctx *ctx, const int32_t *z);
 int isg_set_freq(isg_ctx *ctx, const double *freq);
 int isg_set_qq(isg_ctx *ctx, const double *qq);
 int isg_set_generation(isg_ctx *ctx, const int32_t *gen);
-int isg_set_self_rates(isg_ctx *ctx, const double *s);
+int isg_set_self_rates(isg_ctx *ctx, const double *s);   /* per-cluster rates with -e 0: also sets the MH state, dt_stat of each rate (a rate beyond [0,1] is refused) */
 int isg_set_alpha(isg_ctx *ctx, double alpha);
 
 /*

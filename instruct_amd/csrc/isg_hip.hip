@@ -3065,6 +3065,13 @@ extern "C" int isg_set_self_rates(isg_ctx *c, const double *s)
 {
 	HIPCHK(hipSetDevice(c->cfg.device));
 	if (ensure_S(c)) return 1;
+	const bool per_cluster = c->poly || c->cfg.mode == 2 || c->cfg.mode == 4;
+	if (per_cluster && c->cfg.back_refl == 0) { /* the MH state goes with the rates, as where chain_init writes them (mcmc.c:200, poly_geno.c:93) */
+		for (int k = 0; k < c->cfg.K; k++)
+			if (isg_dt_stat(s[k]) < 0) return fail("The value of selfing rate or inbreeding coefficient is beyond [0,1]!");
+		for (int k = 0; k < c->cfg.K; k++) c->state[k] = isg_dt_stat(s[k]);
+		HIPCHK(hipMemcpy(c->d_state, c->state.data(), sizeof(int) * c->cfg.K, hipMemcpyHostToDevice));
+	}
 	memcpy(c->S.data(), s, sizeof(double) * c->S.size());
 	HIPCHK(hipMemcpy(c->d_S, c->S.data(), sizeof(double) * c->S.size(), hipMemcpyHostToDevice));
 	return 0;

@@ -12,7 +12,9 @@
  * (:2122-2304), choose_two/tri/tetra_allo (:962-1215) and the two-subgenome terms of calc_genofq (:1262-1282); pinned to
  * tests/golden/ta*.golden the same way.
  *
- * usage (dump tool, main() below): orc_dump_poly data.txt out K N L u b t e r j s1 s2 s3 [math accum [keyed [allo]]]
+ * usage (dump tool, main() below): orc_dump_poly data.txt out K N L u b t e r j s1 s2 s3 [math accum [keyed [allo [state]]]]
+ * state: a file of hexadecimal doubles (alpha, K selfing rates, N x K qq; nan = keep) written into the chain before iteration 0 -- see
+ * inject_state() below and tests/converged_poly.py.  Without it the output is what it was before the argument existed.
  */
 #include <math.h>
 #include <stdint.h>
@@ -726,9 +728,64 @@ static uint64_t hash_tables(float **tab)
 			for (g = 0; g < gtot(j); g++) h = fnv_bytes(h, &tab[k * L + j][g], 4);
 	return h;
 }
+/* State injection (tests/converged_poly.py): alpha, K selfing rates, N x K qq (nan = keep the chain's own value), read after `chain zqinit`
+ * and before iteration 0; no uniform is consumed.  With -e 0 the MH states follow the rates as where the chain sets them up. */
+static int inject_state(const char *path, FILE *G)
+{
+	FILE *f = fopen(path, "r");
+	double v;
+	long i;
+	if (!f) return -1;
+	if (fscanf(f, "%la", &v) != 1) { fclose(f); return -1; }
+	if (!isnan(v)) alpha = v;
+	for (i = 0; i < K; i++) {
+		if (fscanf(f, "%la", &v) != 1) { fclose(f); return -1; }
+		if (!isnan(v)) S[i] = v;
+		if (back_refl == 0) state[i] = dt_stat(S[i]);
+	}
+	for (i = 0; i < (long)N * K; i++) {
+		if (fscanf(f, "%la", &v) != 1) { fclose(f); return -1; }
+		if (!isnan(v)) qq[i] = v;
+	}
+	fclose(f);
+	fprintf(G, "chain injected alpha=%a hqq=%016llx", alpha, (unsigned long long)hash_f64v(qq, (long)N * K));
+	for (i = 0; i < K; i++) fprintf(G, " %a", S[i]);
+	if (back_refl == 0) for (i = 0; i < K; i++) fprintf(G, " st%d", state[i]);
+	fprintf(G, "\n");
+	return 0;
+}
+/* the regime an iteration ended in (only written with a state file): share of the used loci whose four Z copies sit in one cluster,
+ * exact zeros in qq, smallest nonzero qq, clusters with sum qq < 0.01, NaN / infinite genofreq entries, totallkh finite */
+static void dump_regime(FILE *G, long step)
+{
+	long used = 0, same = 0, zeros = 0, nn = 0, ni = 0;
+	int i, j, k, g, empty = 0;
+	double qmin = 1.0;
+	for (i = 0; i < N; i++)
+		for (j = 0; j < L; j++)
+			if (VALID(i, j)) { used++; same += chcksame(&Z(i, j, 0), P4) == 0; }
+	for (i = 0; i < N * K; i++) {
+		if (qq[i] == 0) zeros++;
+		else if (qq[i] < qmin) qmin = qq[i];
+	}
+	for (k = 0; k < K; k++) {
+		double sum = 0;
+		for (i = 0; i < N; i++) sum += qq[(long)i * K + k];
+		if (sum < 0.01) empty++;
+	}
+	for (k = 0; k < K; k++)
+		for (j = 0; j < L; j++)
+			for (g = 0; g < gtot(j); g++) {
+				if (isnan(genofreq[k * L + j][g])) nn++;
+				else if (isinf(genofreq[k * L + j][g])) ni++;
+			}
+	fprintf(G, "reg %ld same=%.6f zeros=%ld qmin=%a empty=%d nan=%ld inf=%ld lkhfinite=%d\n", step, used ? (double)same / (double)used : 0.0, zeros, qmin,
+		empty, nn, ni, isfinite(totallkh) ? 1 : 0);
+}
 int main(int argc, char **argv)
 {
 	FILE *G;
+	const char *state_path = NULL;
 	dump_dims D;
 	int *vflat, *gflat, *cflat, e, r, jj, s1, s2, s3, t, i, j, k;
 	long u, b, step, cnt_step = 0;
@@ -738,10 +795,11 @@ int main(int argc, char **argv)
 	double c_tot = 1, c_tot2 = 1, *c_indv, *c_S, *c_qq;
 	long c_step = 0, steps;
 	int flag_empty = 0;
-	if (argc != 15 && argc != 17 && argc != 18 && argc != 19) { fprintf(stderr, "usage: orc_dump_poly data out K N L u b t e r j s1 s2 s3 [math accum [keyed [allo]]]\n"); return 2; }
+	if (argc != 15 && argc != 17 && argc != 18 && argc != 19 && argc != 20) { fprintf(stderr, "usage: orc_dump_poly data out K N L u b t e r j s1 s2 s3 [math accum [keyed [allo [state]]]]\n"); return 2; }
 	if (argc >= 17) { g_math = atoi(argv[15]); g_accum = atoi(argv[16]); }
 	if (argc >= 18) g_keyed = atoi(argv[17]);
-	if (argc == 19) g_allo = atoi(argv[18]);
+	if (argc >= 19) g_allo = atoi(argv[18]);
+	if (argc == 20) state_path = argv[19];
 	K = atoi(argv[3]); u = atol(argv[6]); b = atol(argv[7]); t = atoi(argv[8]); e = atoi(argv[9]); r = atoi(argv[10]); jj = atoi(argv[11]);
 	s1 = atoi(argv[12]); s2 = atoi(argv[13]); s3 = atoi(argv[14]);
 	back_refl = e;
@@ -790,6 +848,7 @@ int main(int argc, char **argv)
 	for (i = 0; i < K; i++) { S[i] = initd[i]; if (back_refl == 0) state[i] = dt_stat(S[i]); }
 	update_ZQ(1);
 	fprintf(G, "chain zqinit hz=%016llx hqq=%016llx", (unsigned long long)hash_z(&D, z), (unsigned long long)hash_f64v(qq, (long)N * K)); SEEDS();
+	if (state_path && inject_state(state_path, G)) { fprintf(stderr, "orc_dump_poly: cannot read the state file %s\n", state_path); return 2; }
 	for (step = 0; step < u; step++) {
 		ky_iter = (uint64_t)step;
 		if (g_allo) update_P_allo();
@@ -814,6 +873,7 @@ int main(int argc, char **argv)
 		fprintf(G, "it %ld GE hgeno=%016llx", step, (unsigned long long)hash_i32v(gflat, (long)N * L * P4)); SEEDS();
 		totallkh = cal_lkd();
 		fprintf(G, "it %ld L totallkh=%a hindv=%016llx\n", step, totallkh, (unsigned long long)hash_f64v(indvlkh, N));
+		if (state_path) dump_regime(G, step);
 		if (step == b - 1) {
 			c_step = 0; c_tot = 1; c_tot2 = 1;
 			for (i = 0; i < N; i++) c_indv[i] = 1;

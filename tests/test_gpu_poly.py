@@ -39,7 +39,7 @@ def extra_data(name):
     return synth.raw_alleles(N, L, K, 4, A, miss, 20260301 + sorted(EXTRA).index(name))
 
 
-def hip_lines(name, cfg=None, raw=None, sched=0, fast_coder=False, allo=False):
+def hip_lines(name, cfg=None, raw=None, sched=0, fast_coder=False, allo=False, after_init=None):
     """Drives the C ABI sweep by sweep and formats the state as oracle/isg_oracle_poly.c's dump does."""
     from instruct_amd import capi, synth
     N, L, K, A, miss, u, b, t, e, r, j, seeds = cfg or (ALLO[name] if allo else POLY[name])
@@ -55,6 +55,8 @@ def hip_lines(name, cfg=None, raw=None, sched=0, fast_coder=False, allo=False):
     # the reference draws alpha, imputes the genotypes, then update_ZQ(1): chain_init does the three
     ch.chain_init(initd)
     lines.append("chain zqinit hz=%s hqq=%s" % (orc.fnv_i32(ch.z()), orc.fnv_f64(ch.qq())) + sd())
+    if after_init is not None:   # (tests/converged_poly.py: a state written into the chain; the lines it reports, if any)
+        lines.extend(after_init(ch) or [])
     for step in range(u):
         ch.update_P()
         lines.append("it %d P hcnt=%s hfreq=%s" % (step, _hcnt(ch, allelenum), _hfreq(ch, allelenum)) +

@@ -35,7 +35,7 @@ def wide_data(name):
     return mga.panel(N, sizes, K, miss, 20261030 + sorted(WIDE).index(name))
 
 
-def hip_lines(cfg, raw, sched=0, allo=False):
+def hip_lines(cfg, raw, sched=0, allo=False, after_init=None):
     """Drives the C ABI sweep by sweep and formats the state as oracle/isg_oracle_poly.c's dump does (as tests/test_gpu_poly.py)."""
     from instruct_amd import capi, synth
     N, L, K, A, miss, u, b, t, e, r, j, seeds = cfg[:12]
@@ -47,6 +47,8 @@ def hip_lines(cfg, raw, sched=0, allo=False):
     sd = lambda: " seeds=%d %d %d" % ch.seeds()
     ch.chain_init(initd)
     lines.append("chain zqinit hz=%s hqq=%s" % (orc.fnv_i32(ch.z()), orc.fnv_f64(ch.qq())) + sd())
+    if after_init is not None:   # (tests/converged_poly.py: a state written into the chain; the lines it reports, if any)
+        lines.extend(after_init(ch) or [])
     for step in range(u):
         ch.update_P()
         lines.append("it %d P hcnt=%s hfreq=%s" % (step, _hcnt(ch, allelenum), _hfreq(ch, allelenum)) +
