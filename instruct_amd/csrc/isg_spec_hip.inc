@@ -421,8 +421,14 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 		walk_launch_tables(c, w, in, s, "k_wk_table_Z");
 		walk_launch_walk(c, w, in, s, 0, 0, "k_wk_walk_Z");
 	}
+	/* three-launch walk: the first launch of a second walk zeroes the list counters and the state's per-walk tail itself (it runs behind
+	 * k_zq_probe, which reads the counters, and ahead of k_wk_down and k_zs_band, which add to both); before the sweep's first k_zs_band the
+	 * prologue's memset of all of SpecDev still holds, nothing has written it since */
+	const bool fused = walk_fused(w);
+	WalkZero zero;
+	zero.words = (unsigned *)sp->d_dev.get(); zero.n = 2; zero.tail = true;
 	auto list_on_path = [&]() { /* the uncertain bytes on the current trajectory (band = 0) */
-		(void)hipMemsetAsync(sp->d_dev, 0, 2 * sizeof(unsigned), c->stream);
+		if (!fused) (void)hipMemsetAsync(sp->d_dev, 0, 2 * sizeof(unsigned), c->stream);
 		const long nthr = (long)N * (2 * sp->band + 1);
 		prof_begin(c);
 		hipLaunchKernelGGL(k_zs_band, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, c->stream, (const WkBlock *)w.d_blk, (const WkSeg *)w.d_seg, nseg, (const unsigned char *)w.d_table,
@@ -433,8 +439,8 @@ static int spec_update_ZQ_once(isg_ctx *c, SpecCtx *sp, isg_wh base, bool *done,
 		prof_begin(c);
 		launch_probe(1024);
 		prof_end(c, "k_zq_probe");
-		(void)hipMemsetAsync((char *)w.d_st.get() + offsetof(WkState, sum_d), 0, sizeof(WkState) - offsetof(WkState, sum_d), c->stream);
-		for (int s = 0; s < nseg; s++) walk_launch_walk(c, w, in, s, 0, 1, "k_wk_walk_Z");
+		if (!fused) (void)hipMemsetAsync((char *)w.d_st.get() + offsetof(WkState, sum_d), 0, sizeof(WkState) - offsetof(WkState, sum_d), c->stream);
+		for (int s = 0; s < nseg; s++) walk_launch_walk(c, w, in, s, 0, 1, "k_wk_walk_Z", (fused && s == 0) ? &zero : nullptr);
 		list_on_path();
 	};
 	auto finish = [&]() {

@@ -627,6 +627,10 @@ typedef struct {
 	const float *bpred;       /* statistics: the blocks' predicted rejections ... */
 	const int *gam0;          /* ... and gammas */
 	float scale;
+	/* the three-launch walk (wk_compose2_body, wk_down_body; the five bodies above them read none of these): */
+	unsigned *fail_in;        /* st->fail as the segment's up pass found it: wk_down adds to st->fail itself and must not read it */
+	unsigned *zero_words;     /* wk_zero_body: nzero words to zero before a second walk (null / 0: none) ... */
+	int nzero, zero_tail;     /* ... and whether the per-walk tail of WkState goes with them */
 } WkWalkArgs;
 
 /* n 16-byte words from global memory into LDS, all threads (both 16-byte aligned) */
@@ -855,6 +859,328 @@ ISG_HD void wk_final_body(const WkWalkArgs A, int wg, int nthreads, unsigned cha
 				if (B.g0 + B.ng == A.total_groups) A.T[A.total_groups] = (unsigned long long)((long long)xin + (long long)(B.wlo + col));
 			}
 		}
+	}
+}
+
+/* ---------------------------------------------------------------------------------------------------------------- */
+/* the walk in three launches: wk_block, wk_compose2, wk_down                                                         */
+/* ---------------------------------------------------------------------------------------------------------------- */
+/*
+ * The same maps, entries, offsets and statistics as the five bodies above, which stay the statement they are tested against
+ * (tests/emul/walk_down_emul.cpp).  What differs is where the loads stand: descriptors are staged into LDS before the maps, the maps in
+ * one flattened loop over (map, 16-byte word) with four loads in flight per thread, and a chain reads LDS only.  The way down is one
+ * launch: every block's workgroup walks the segment's F2 maps and the F1 maps of the blocks before it in its super-block itself -- a few
+ * dozen LDS steps -- instead of waiting two launches for one lane to do it for all.  They rely on what wk_plan_build lays out:
+ * super-block k of a segment holds the blocks b0 + k WK_FAN .. (wk_plan_fused_ok checks it).
+ */
+#if defined(__HIP_DEVICE_COMPILE__)
+/* a byte through a pointer of a stated address space: a select between an LDS and a global address would make the load a flat one */
+#define WK_LDS_U8(p, i) (((const __attribute__((address_space(3))) unsigned char *)(p))[i])
+#define WK_GLB_U8(p, i) (((const __attribute__((address_space(1))) unsigned char *)(p))[i])
+#else
+#define WK_LDS_U8(p, i) (((const unsigned char *)(p))[i])
+#define WK_GLB_U8(p, i) (((const unsigned char *)(p))[i])
+#endif
+
+/* nmaps maps into LDS back to back: map k starts at maps + foff[k] and is pre[k + 1] - pre[k] 16-byte words long (foff, pre: in LDS) */
+ISG_HD void wk_stage_maps(unsigned short *L, const unsigned short *maps, const unsigned *foff, const int *pre, int nmaps, int t, int nthreads)
+{
+	const int tot = pre[nmaps];
+	int k = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+	/* (named registers, not an array: an indexed array of loads ends up in scratch) */
+#define WK_SM_LOAD(v, iq) do { if ((iq) < tot) { while ((iq) >= pre[k + 1]) k++; v = ((const uint4 *)(maps + foff[k]))[(iq) - pre[k]]; } } while (0)
+	uint4 *d4 = (uint4 *)L;
+	for (int i = t; i < tot; i += 4 * nthreads) { /* four loads in flight per thread, whichever maps they fall into */
+		const int i1 = i + nthreads, i2 = i + 2 * nthreads, i3 = i + 3 * nthreads;
+		uint4 a = make_uint4(0, 0, 0, 0), b = a, c = a, d = a;
+		WK_SM_LOAD(a, i);
+		WK_SM_LOAD(b, i1);
+		WK_SM_LOAD(c, i2);
+		WK_SM_LOAD(d, i3);
+		d4[i] = a;
+		if (i1 < tot) d4[i1] = b;
+		if (i2 < tot) d4[i2] = c;
+		if (i3 < tot) d4[i3] = d;
+	}
+#undef WK_SM_LOAD
+#else
+	for (int i = t; i < tot; i += nthreads) {
+		while (i >= pre[k + 1]) k++;
+		memcpy((char *)L + 16 * (size_t)i, (const char *)(maps + foff[k]) + 16 * (size_t)(i - pre[k]), 16);
+	}
+#endif
+}
+
+/* before a second walk over the same tables (its first segment's first launch): thread 0 of workgroup 0 zeroes what memsets would */
+ISG_HD void wk_zero_body(const WkWalkArgs A, int wg, int nthreads)
+{
+	WK_THREADS(t, nthreads) {
+		if (wg == 0 && t == 0) {
+			for (int i = 0; i < A.nzero; i++) A.zero_words[i] = 0u;
+			if (A.zero_tail) {
+				A.st->sum_d = 0ull;
+				A.st->nblk = 0ull;
+				A.st->resid2 = 0.0;
+				A.st->ngam = 0.0;
+			}
+		}
+	}
+}
+
+/* wk_compose2: wk_compose with the super-block's descriptors in LDS (WK_C2_HDR bytes), the maps behind them; workgroup 0 notes st->fail */
+#define WK_C2_HDR ((int)((sizeof(WkBlock) * WK_FAN + sizeof(unsigned) * WK_FAN + sizeof(int) * (WK_FAN + 1) + 15) & ~(size_t)15))
+ISG_HD void wk_compose2_body(const WkWalkArgs A, int wg, int nthreads, unsigned char *lds)
+{
+	const WkSuper S = A.sup[A.seg.s0 + wg];
+	const int b0 = A.seg.b0 + wg * WK_FAN;
+	const int nb = (A.seg.nb - wg * WK_FAN < WK_FAN) ? A.seg.nb - wg * WK_FAN : WK_FAN;
+	WkBlock *own = (WkBlock *)lds;
+	unsigned *foff = (unsigned *)(own + WK_FAN);
+	int *pre = (int *)(foff + WK_FAN);
+	unsigned short *L = (unsigned short *)(lds + WK_C2_HDR);
+	WK_THREADS(t, nthreads) {
+		for (int k = t; k < nb; k += nthreads) own[k] = A.blk[b0 + k];
+		if (wg == 0 && t == 0) *A.fail_in = A.st->fail;
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		for (int k = t; k <= nb; k += nthreads) {
+			int w = 0;
+			for (int q = 0; q < k; q++) w += WK_EIN8(own[q].ein) / 8;
+			pre[k] = w;
+			if (k < nb) foff[k] = own[k].foff;
+		}
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		wk_stage_maps(L, A.maps, foff, pre, nb, t, nthreads);
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		const int wlo0 = own[0].wlo, ein0 = own[0].ein;
+		unsigned short *F2 = A.maps + S.foff;
+		for (int e = t; e < ein0; e += nthreads) {
+			int x = wlo0 + e, ok = 1;
+			for (int k = 0; k < nb; k++) {
+				const int col = x - own[k].wlo;
+				if (col < 0 || col >= own[k].ein) { ok = 0; break; }
+				const unsigned d = L[8 * pre[k] + col];
+				if (d == WK_OUT16) { ok = 0; break; }
+				x += (int)d;
+			}
+			const int d = x - (wlo0 + e);
+			F2[e] = (!ok || d >= (int)WK_OUT16) ? (unsigned short)WK_OUT16 : (unsigned short)d;
+		}
+	}
+}
+
+/* LDS of wk_down (offsets in bytes): the descriptors, the block's offsets, its strip, then one region for the F2 and later the F1 maps */
+typedef struct {
+	int sup, b0s, own; /* WkSuper[ns]; WkBlock[ns]: the first block of every super-block; WkBlock[WK_FAN]: the own super-block's up to this one */
+	int foff, pre, es; /* wk_stage_maps' two arrays [max(ns, WK_FAN) (+ 1)]; int[ns]: the super-blocks' entries */
+	int misc;          /* int[4]: the segment's exit offset, whether the path through it holds, this block's entry, offsets in T */
+	int T, strip, maps;
+} WkDownLds;
+ISG_HD WkDownLds wk_down_layout(int ns)
+{
+	const int nm = ns > WK_FAN ? ns : WK_FAN;
+	WkDownLds o;
+	o.sup = 0;
+	o.b0s = o.sup + (int)sizeof(WkSuper) * ns;
+	o.own = o.b0s + (int)sizeof(WkBlock) * ns;
+	o.foff = o.own + (int)sizeof(WkBlock) * WK_FAN;
+	o.pre = o.foff + 4 * nm;
+	o.es = o.pre + 4 * (nm + 1);
+	o.misc = o.es + 4 * ns;
+	o.T = (o.misc + 16 + 15) & ~15;
+	o.strip = o.T + 8 * WK_BG;
+	o.maps = o.strip + WK_BG * WK_STRIP;
+	return o;
+}
+/* maps_bytes: the larger of the segment's F2 maps and the F1 maps of a super-block without its last block */
+ISG_HD size_t wk_down_lds_bytes(int ns, size_t maps_bytes) { return (size_t)wk_down_layout(ns).maps + maps_bytes; }
+
+/* wk_down: workgroup per block of the segment: wk_top's walk, wk_expand's as far as this block, wk_final's through its rows.  Workgroup 0
+ * writes what wk_top writes; no workgroup reads what another writes in this launch. */
+ISG_HD void wk_down_body(const WkWalkArgs A, int wg, int nthreads, unsigned char *lds)
+{
+	const int ns = A.seg.ns, b = A.seg.b0 + wg, ks = wg / WK_FAN, kb = wg % WK_FAN;
+	const WkDownLds o = wk_down_layout(ns);
+	WkSuper *sup = (WkSuper *)(lds + o.sup);
+	WkBlock *b0s = (WkBlock *)(lds + o.b0s), *own = (WkBlock *)(lds + o.own);
+	unsigned *foff = (unsigned *)(lds + o.foff);
+	int *pre = (int *)(lds + o.pre), *es = (int *)(lds + o.es), *misc = (int *)(lds + o.misc);
+	unsigned long long *Tl = (unsigned long long *)(lds + o.T);
+	unsigned char *strip = lds + o.strip;
+	unsigned short *L = (unsigned short *)(lds + o.maps);
+	/* what the chains take from global memory, asked for before anything is waited for */
+	const WkBlock B = A.blk[b];
+	const unsigned long long xin = A.st->xin[A.segno];
+	const long long ent0 = A.st->ent[A.segno];
+	const unsigned fail_in = *A.fail_in;
+	const float bp = A.bpred[b];
+	const int gam_a = A.gam0[B.g0], gam_b = A.gam0[B.g0 + B.ng];
+	const int W = B.W;
+	WK_THREADS(t, nthreads) {
+		for (int i = t; i < 2 * ns + kb + 1; i += nthreads) {
+			if (i < ns) sup[i] = A.sup[A.seg.s0 + i];
+			else if (i < 2 * ns) b0s[i - ns] = A.blk[A.seg.b0 + (i - ns) * WK_FAN];
+			else own[i - 2 * ns] = A.blk[A.seg.b0 + ks * WK_FAN + (i - 2 * ns)];
+		}
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		for (int k = t; k <= ns; k += nthreads) {
+			int w = 0;
+			for (int q = 0; q < k; q++) w += WK_EIN8(b0s[q].ein) / 8;
+			pre[k] = w;
+			if (k < ns) foff[k] = sup[k].foff;
+		}
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		wk_stage_maps(L, A.maps, foff, pre, ns, t, nthreads);
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		if (t == 0) { /* wk_top's walk: every workgroup takes all ns steps (a failed path leaves no block with an entry) */
+			int x = (int)ent0, ok = fail_in ? 0 : 1;
+			for (int k = 0; k < ns && ok; k++) {
+				const int col = x - b0s[k].wlo;
+				es[k] = x;
+				if (col < 0 || col >= b0s[k].ein) { ok = 0; break; }
+				const unsigned d = L[8 * pre[k] + col];
+				if (d == WK_OUT16) { ok = 0; break; }
+				x += (int)d;
+			}
+			misc[0] = x;
+			misc[1] = ok;
+		}
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		const int x = misc[0], ok = misc[1];
+		if (wg == 0) {
+			for (int k = t; k < ns; k += nthreads) A.ent_sup[A.seg.s0 + k] = ok ? es[k] : WK_NOENT;
+			if (t == 0) {
+				if (!ok) {
+					WK_ATOMIC_OR(&A.st->fail, 1u);
+					if (!A.keep_origin) A.st->xin[A.segno + 1] = xin;
+				} else if (!A.keep_origin) {
+					A.st->xin[A.segno + 1] = xin + (unsigned long long)x;
+					A.st->ent[A.segno + 1] = 0;
+				} else {
+					A.st->ent[A.segno + 1] = (long long)(xin + (unsigned long long)x) - (long long)A.st->xin[A.segno + 1];
+				}
+			}
+		}
+		/* the F1 maps of the blocks before this one (none if its super-block has no entry) */
+		const int none = !ok;
+		for (int k = t; k <= kb; k += nthreads) {
+			int w = 0;
+			for (int q = 0; q < k; q++) w += WK_EIN8(own[q].ein) / 8;
+			pre[k] = none ? 0 : w;
+			if (k < kb) foff[k] = own[k].foff;
+		}
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		wk_stage_maps(L, A.maps, foff, pre, kb, t, nthreads);
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		if (t == 0) { /* wk_expand's walk as far as this block */
+			int x = misc[1] ? es[ks] : WK_NOENT, ok = (x != WK_NOENT);
+			for (int k = 0; k < kb && ok; k++) {
+				const int col = x - own[k].wlo;
+				if (col < 0 || col >= own[k].ein || L[8 * pre[k] + col] == WK_OUT16) ok = 0;
+				else x += (int)L[8 * pre[k] + col];
+			}
+			const int ent = ok ? x : WK_NOENT;
+			misc[2] = ent;
+			A.ent_blk[b] = ent;
+		}
+	}
+	WK_SYNC();
+	/* wk_final: the strip of the block's table from the entry column on, every thread's loads issued before the first is waited for */
+	WK_THREADS(t, nthreads) {
+		const int ent = misc[2];
+		if (ent != WK_NOENT && ent >= B.wlo && ent - B.wlo < W) {
+			const int c0 = (ent - B.wlo) & ~15;
+			const int cw = (W - c0 > WK_STRIP) ? WK_STRIP : W - c0;
+			const int n16 = cw / 16, nk = B.ng * (WK_STRIP / 16);
+			const unsigned char *src = A.table + B.toff + c0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WK_ST_LOAD(v, j) do { const int k_ = k0 + (j) * nthreads; if (k_ < nk && k_ % (WK_STRIP / 16) < n16) v = *(const uint4 *)(src + (size_t)(k_ / (WK_STRIP / 16)) * W + 16 * (k_ % (WK_STRIP / 16))); } while (0)
+#define WK_ST_STORE(v, j) do { const int k_ = k0 + (j) * nthreads; if (k_ < nk && k_ % (WK_STRIP / 16) < n16) *(uint4 *)(strip + (k_ / (WK_STRIP / 16)) * WK_STRIP + 16 * (k_ % (WK_STRIP / 16))) = v; } while (0)
+			for (int k0 = t; k0 < nk; k0 += 8 * nthreads) { /* (256 threads, 64 rows: once) */
+				uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0, v2 = v0, v3 = v0, v4 = v0, v5 = v0, v6 = v0, v7 = v0;
+				WK_ST_LOAD(v0, 0); WK_ST_LOAD(v1, 1); WK_ST_LOAD(v2, 2); WK_ST_LOAD(v3, 3);
+				WK_ST_LOAD(v4, 4); WK_ST_LOAD(v5, 5); WK_ST_LOAD(v6, 6); WK_ST_LOAD(v7, 7);
+				WK_ST_STORE(v0, 0); WK_ST_STORE(v1, 1); WK_ST_STORE(v2, 2); WK_ST_STORE(v3, 3);
+				WK_ST_STORE(v4, 4); WK_ST_STORE(v5, 5); WK_ST_STORE(v6, 6); WK_ST_STORE(v7, 7);
+			}
+#undef WK_ST_LOAD
+#undef WK_ST_STORE
+#else
+			for (int k = t; k < nk; k += nthreads) {
+				const int r = k / (WK_STRIP / 16), q = k % (WK_STRIP / 16);
+				if (q < n16) memcpy(strip + r * WK_STRIP + 16 * q, src + (size_t)r * W + 16 * q, 16);
+			}
+#endif
+		}
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		if (t == 0) {
+			const int ent = misc[2];
+			int nT = 0;
+			if (ent != WK_NOENT) {
+				const int c0 = (ent < B.wlo) ? 0 : ((ent - B.wlo) & ~15);
+				int cw = W - c0;
+				if (cw > WK_STRIP) cw = WK_STRIP;
+				if (cw < 0) cw = 0;
+				int col = ent - B.wlo;
+				unsigned why = 0;
+				int r = 0;
+				if (col < 0 || col >= B.ein) why = 1u;
+				for (; r < B.ng && !why; r++) {
+					if (col >= W) { why |= 1u; break; }
+					Tl[r] = (unsigned long long)((long long)xin + (long long)(B.wlo + col)); /* T[g0 + r], stored by lane r below */
+					nT = r + 1;
+					const int q = col - c0;
+					unsigned v;
+					if (q >= 0 && q < cw) v = WK_LDS_U8(strip, r * WK_STRIP + q);
+					else v = WK_GLB_U8(A.table, B.toff + (size_t)r * W + col); /* the path has left the strip */
+					const int c = wk_byte_step(v, A.mode, A.strict, &why);
+					if (c < 0) break;
+					col += c;
+				}
+				if ((why & 2u) && r < B.ng) {
+					int lo, hi;
+					if (wk_trim_range(B, A.gam0[B.g0 + r] - gam_a, gam_b - gam_a, &lo, &hi) && (col < lo || col >= hi)) why = (why & ~2u) | 1u;
+				}
+				if (why) {
+					WK_ATOMIC_OR(&A.st->fail, why);
+					if (!A.st->nfail_block) A.st->nfail_block = (unsigned)b + 1u;
+				} else {
+					const unsigned long long d = (unsigned long long)((long long)(B.wlo + col) - (long long)ent);
+					const double rs = (double)d - (double)(bp * A.scale);
+					WK_ATOMIC_ADD64(&A.st->sum_d, d);
+					WK_ATOMIC_ADD64(&A.st->nblk, 1ull);
+					WK_ATOMIC_ADD_F64(&A.st->resid2, rs * rs);
+					WK_ATOMIC_ADD_F64(&A.st->ngam, (double)(gam_b - gam_a));
+					if (B.g0 + B.ng == A.total_groups) A.T[A.total_groups] = (unsigned long long)((long long)xin + (long long)(B.wlo + col));
+				}
+			}
+			misc[3] = nT;
+		}
+	}
+	WK_SYNC();
+	WK_THREADS(t, nthreads) {
+		const int nT = misc[3];
+		for (int r = t; r < nT; r += nthreads) A.T[B.g0 + r] = Tl[r];
 	}
 }
 

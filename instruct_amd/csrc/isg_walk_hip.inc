@@ -63,6 +63,23 @@ __global__ void __launch_bounds__(256) k_wk_final(WkWalkArgs A)
 	extern __shared__ __attribute__((aligned(16))) unsigned char wk_lds[];
 	wk_final_body(A, (int)blockIdx.x, (int)blockDim.x, wk_lds);
 }
+/* the walk in three launches (isg_walk.h): k_wk_block (k_wk_block_z before a second walk's first segment), k_wk_compose2, k_wk_down */
+__global__ void __launch_bounds__(1024) k_wk_block_z(WkWalkArgs A)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char wk_lds[];
+	wk_zero_body(A, (int)blockIdx.x, (int)blockDim.x);
+	wk_block_body(A, (int)blockIdx.x, (int)blockDim.x, wk_lds);
+}
+__global__ void __launch_bounds__(512) k_wk_compose2(WkWalkArgs A)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char wk_lds[];
+	wk_compose2_body(A, (int)blockIdx.x, (int)blockDim.x, wk_lds);
+}
+__global__ void __launch_bounds__(256) k_wk_down(WkWalkArgs A)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char wk_lds[];
+	wk_down_body(A, (int)blockIdx.x, (int)blockDim.x, wk_lds);
+}
 
 /* one run's device buffers and plan */
 struct WalkRun {
@@ -90,13 +107,18 @@ struct WalkRun {
 	/* the tables' rows are evaluated at the columns a row can be entered at only (wk_trim_range); trim_k: their spread in sigma, 0 = the walk's kwin */
 	bool trim = true;
 	double trim_k = 0.0;
+	/* the walk in three launches (k_wk_block, k_wk_compose2, k_wk_down); false, or a plan that does not fit them: the five launches */
+	bool fused = true, plan_fused = false;
 };
-/* INSTRUCT_WALK_TRIM / INSTRUCT_WALK_TRIM_K, read where a run's context is created */
+/* INSTRUCT_WALK_TRIM / INSTRUCT_WALK_TRIM_K / INSTRUCT_WALK_FUSED, read where a run's context is created */
 static void walk_read_trim_env(WalkRun &w)
 {
 	w.trim = env_flag(getenv("INSTRUCT_WALK_TRIM"), true);
 	w.trim_k = env_double(getenv("INSTRUCT_WALK_TRIM_K"), 0.0, 0.0);
+	w.fused = env_flag(getenv("INSTRUCT_WALK_FUSED"), true);
 }
+#define WK_LDS_LIMIT ((size_t)160 * 1024) /* dynamic LDS a workgroup of the walk kernels may ask for */
+static bool walk_fused(const WalkRun &w) { return w.fused && w.plan_fused; }
 /* the spread the next plan trims its rows with: it widens with the windows after a miss (walk_adapt) */
 static double walk_trim_k(const WalkRun &w)
 {
@@ -135,7 +157,7 @@ static int walk_prepare(isg_ctx *c, WalkRun &w, const int *gam0_h, int G, int mo
 		HIPCHK(w.d_table.grow(np.table_bytes + 64));
 		HIPCHK(w.d_maps.grow(np.maps_elems + 64));
 		HIPCHK(w.d_T.grow((size_t)G + 1));
-		if (!w.d_st) HIPCHK(w.d_st.alloc(1));
+		if (!w.d_st) HIPCHK(w.d_st.alloc(2)); /* (the word behind the state: WkWalkArgs.fail_in) */
 		if (!w.d_seg) HIPCHK(w.d_seg.alloc(WK_MAXSEG));
 		{ /* through one page-aligned staging block (see PageAlloc): the plan's own vectors sit anywhere in the heap */
 			const size_t b0 = sizeof(WkSeg) * np.seg.size(), b1 = sizeof(WkBlock) * np.blk.size(), b2 = sizeof(WkSuper) * np.sup.size(), b3 = sizeof(int) * np.hw.size();
@@ -165,8 +187,12 @@ static int walk_prepare(isg_ctx *c, WalkRun &w, const int *gam0_h, int G, int mo
 		HIPCHK(hipFuncSetAttribute((const void *)k_wk_compose, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 		HIPCHK(hipFuncSetAttribute((const void *)k_wk_top, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 		HIPCHK(hipFuncSetAttribute((const void *)k_wk_expand, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		HIPCHK(hipFuncSetAttribute((const void *)k_wk_block_z, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		HIPCHK(hipFuncSetAttribute((const void *)k_wk_compose2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		HIPCHK(hipFuncSetAttribute((const void *)k_wk_down, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 		w.attrs_set = true;
 	}
+	w.plan_fused = wk_plan_fused_ok(w.plan, WK_LDS_LIMIT);
 	*ok = true;
 	return 0;
 }
@@ -206,14 +232,34 @@ static void walk_launch_tables(isg_ctx *c, WalkRun &w, const WalkInputs &in, int
 	else hipLaunchKernelGGL(k_wk_table<WK_MODE_EXACT>, dim3((unsigned)(S.g1 - S.g0)), dim3(256), tab_off + sizeof(isg_wh_tables), c->stream, A, tab_off);
 	prof_end(c, pname);
 }
+/* what the first launch of a second walk zeroes in place of the caller's memsets (three-launch walk only) */
+struct WalkZero {
+	unsigned *words = nullptr;
+	int n = 0;
+	bool tail = false; /* the per-walk tail of WkState */
+};
 /* the walk through segment s: block maps, super-block maps, the segment, back down to every group */
-static void walk_launch_walk(isg_ctx *c, WalkRun &w, const WalkInputs &in, int s, int strict, int keep_origin, const char *pname)
+static void walk_launch_walk(isg_ctx *c, WalkRun &w, const WalkInputs &in, int s, int strict, int keep_origin, const char *pname, const WalkZero *z = nullptr)
 {
 	const WkSeg S = w.plan.seg[s];
 	WkWalkArgs A;
 	A.blk = w.d_blk; A.sup = w.d_sup; A.table = w.d_table; A.maps = w.d_maps; A.ent_sup = w.d_ent_sup; A.ent_blk = w.d_ent_blk; A.T = w.d_T; A.st = w.d_st;
 	A.seg = S; A.segno = s; A.mode = w.mode; A.strict = strict; A.keep_origin = keep_origin; A.total_groups = w.plan.groups; A.bpred = w.d_bpred; A.gam0 = in.gam0; A.scale = w.scale;
+	A.fail_in = (unsigned *)(w.d_st.get() + 1);
+	A.zero_words = nullptr; A.nzero = 0; A.zero_tail = 0;
 	prof_begin(c);
+	if (walk_fused(w)) {
+		if (z) {
+			A.zero_words = z->words; A.nzero = z->n; A.zero_tail = z->tail ? 1 : 0;
+			hipLaunchKernelGGL(k_wk_block_z, dim3((unsigned)S.nb), dim3(1024), w.plan.lds_block, c->stream, A);
+		} else {
+			hipLaunchKernelGGL(k_wk_block, dim3((unsigned)S.nb), dim3(1024), w.plan.lds_block, c->stream, A);
+		}
+		hipLaunchKernelGGL(k_wk_compose2, dim3((unsigned)S.ns), dim3(512), w.plan.lds_compose + (size_t)WK_C2_HDR, c->stream, A);
+		hipLaunchKernelGGL(k_wk_down, dim3((unsigned)S.nb), dim3(256), w.plan.lds_down, c->stream, A);
+		prof_end(c, pname);
+		return;
+	}
 	hipLaunchKernelGGL(k_wk_block, dim3((unsigned)S.nb), dim3(1024), w.plan.lds_block, c->stream, A);
 	hipLaunchKernelGGL(k_wk_compose, dim3((unsigned)S.ns), dim3(512), w.plan.lds_compose, c->stream, A);
 	hipLaunchKernelGGL(k_wk_top, dim3(1), dim3(512), w.plan.lds_top, c->stream, A);

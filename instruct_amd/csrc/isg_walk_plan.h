@@ -19,6 +19,7 @@ struct WkPlan {
 	size_t table_bytes = 0;   /* of the largest segment (reuse = true) or of all of them */
 	size_t maps_elems = 0;    /* 16-bit deltas, likewise */
 	size_t lds_table = 0, lds_block = 0, lds_compose = 0, lds_top = 0;
+	size_t lds_down = 0;      /* wk_down_body: its descriptors, strip and offsets + the larger of a segment's F2 maps and the F1 maps it stages */
 	int groups = 0, ngmax = 0;
 	double rho_hi = 0, sigma = 0, kwin = 0;
 	double trim_k = 0;        /* a row's reachable columns are taken +-trim_k sigma sqrt(gammas before it in its block) wide (0: rows are not trimmed) */
@@ -107,7 +108,7 @@ static bool wk_plan_build(WkPlan &P, const int *gam0, int G, double rho_hi, doub
 			}
 			/* super-blocks and their maps */
 			std::vector<WkSuper> sup;
-			size_t lds_compose = 0, lds_top = 0;
+			size_t lds_compose = 0, lds_top = 0, lds_f1 = 0; /* lds_f1: a super-block's F1 maps without its last block's (wk_down stages those before a block) */
 			for (size_t k = 0; k < blk.size(); k += WK_FAN) {
 				WkSuper S;
 				S.b0 = (int)(P.blk.size() + k);
@@ -118,6 +119,7 @@ static bool wk_plan_build(WkPlan &P, const int *gam0, int G, double rho_hi, doub
 				size_t lc = 0;
 				for (int q = 0; q < S.nb; q++) lc += 2 * (size_t)WK_EIN8(blk[k + q].ein);
 				if (lc > lds_compose) lds_compose = lc;
+				if (lc - 2 * (size_t)WK_EIN8(blk[k + S.nb - 1].ein) > lds_f1) lds_f1 = lc - 2 * (size_t)WK_EIN8(blk[k + S.nb - 1].ein);
 				lds_top += 2 * (size_t)WK_EIN8(blk[k].ein);
 				sup.push_back(S);
 			}
@@ -155,8 +157,28 @@ static bool wk_plan_build(WkPlan &P, const int *gam0, int G, double rho_hi, doub
 			if (lds_table > P.lds_table) P.lds_table = lds_table;
 			if (lds_compose > P.lds_compose) P.lds_compose = lds_compose;
 			if (lds_top > P.lds_top) P.lds_top = lds_top;
+			{
+				const size_t ld = wk_down_lds_bytes((int)sup.size(), lds_top > lds_f1 ? lds_top : lds_f1);
+				if (ld > P.lds_down) P.lds_down = ld;
+			}
 			g = g1;
 			break;
+		}
+	}
+	return true;
+}
+
+/* Whether a plan can take the three-launch walk (wk_compose2_body, wk_down_body): wk_down's LDS fits `lds_limit` bytes, and super-block k of
+ * a segment holds the blocks b0 + k WK_FAN .. as those bodies assume.  If not, the five launches do the same. */
+static bool wk_plan_fused_ok(const WkPlan &P, size_t lds_limit)
+{
+	if (P.seg.empty() || P.lds_down > lds_limit || P.lds_compose + (size_t)WK_C2_HDR > lds_limit) return false;
+	for (const WkSeg &S : P.seg) {
+		if (S.ns != (S.nb + WK_FAN - 1) / WK_FAN) return false;
+		for (int k = 0; k < S.ns; k++) {
+			const WkSuper &U = P.sup[(size_t)S.s0 + k];
+			const int nb = (S.nb - k * WK_FAN < WK_FAN) ? S.nb - k * WK_FAN : WK_FAN;
+			if (U.b0 != S.b0 + k * WK_FAN || U.nb != nb) return false;
 		}
 	}
 	return true;
