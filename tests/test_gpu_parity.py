@@ -319,6 +319,199 @@ def test_replay_host_update_P_request_is_dropped_when_stale_bit_exact_vs_canonic
     h.close()
 
 
+def _twice(h, names):
+    for n in names:
+        a, b = getattr(h, n)(), getattr(h, n)()
+        assert np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b, n
+
+
+def _diploid_read_write_orders(mode, sched):
+    N, L, K = 12, 300, 2
+    geno, an, mi = synth.code_diploid(synth.raw_alleles(N, L, K, 2, 2, 0.1, 29))
+    h, o, initd = _pair(geno, an, mi, K, sched, mode)
+    pos = ["seeds"] if sched == capi.SCHED_REPLAY else []
+    lkh = ["indvlkh", "totallkh"]
+    # mode 0 keeps zz in the generation slots and has neither qq nor alpha (tests above)
+    state = (["z", "generation", "freq"] if mode == 0 else ["z", "qq", "qqnum", "generation", "alpha", "self_rates", "freq"] + (["state"] if mode in (2, 4) else [])) + lkh + pos
+
+    def iteration(where):
+        h.iteration()
+        o.iteration()
+        _same(h, o, state, where)
+
+    h.chain_init(initd)
+    o.chain_init(initd)
+    iteration("first")
+    _twice(h, ["z", "count_alleles", "freq", "qq", "qqnum", "generation", "self_rates", "state", "indvlkh", "alpha", "totallkh", "seeds"])
+    _same(h, o, state, "read twice")
+
+    def set_z_and_zz():   # mode 0: Z mirrors zz, which the generation slots hold: one write of both
+        z, g = h.z(), h.generation()
+        z, g = np.where(z >= 0, K - 1 - z, z), K - 1 - g
+        for c in (h, o):
+            c.set_z(z)
+            c.set_generation(g)
+        assert np.array_equal(h.z(), z) and np.array_equal(h.generation(), g)
+
+    def set_z():
+        z = h.z()
+        z = np.where(z >= 0, K - 1 - z, z)
+        h.set_z(z)
+        o.set_z(z)
+        assert np.array_equal(h.z(), z)
+
+    def set_freq():
+        f = np.ascontiguousarray(h.freq()[::-1])
+        h.set_freq(f)
+        o.freq()[...] = f
+        assert np.array_equal(h.freq(), f)
+
+    def set_qq():
+        q = 0.5 * h.qq()[:, ::-1] + 0.5 / K
+        num = h.qqnum()
+        h.set_qq(q)
+        o.set_qq(q)
+        assert np.array_equal(h.qq(), q) and np.array_equal(h.qqnum(), num)
+
+    def set_generation():   # (stays within 1..50, the range update_G's tables are built for)
+        g = h.generation()
+        g = np.where(g > 1, g - 1, g + 1).astype(np.int32)
+        h.set_generation(g)
+        o.set_generation(g)
+        assert np.array_equal(h.generation(), g)
+
+    def set_self_rates():
+        r = 0.5 * h.self_rates() + 0.2
+        h.set_self_rates(r)
+        o.set_self_rates(r)
+        assert np.array_equal(h.self_rates(), r)
+
+    def set_alpha():
+        a = 0.5 * h.alpha() + 0.3
+        h.set_alpha(a)
+        o.set_alpha(a)
+        assert h.alpha() == a
+
+    for setter in (set_z_and_zz if mode == 0 else set_z, set_freq, set_qq, set_z_and_zz if mode == 0 else set_generation, set_self_rates, set_alpha):
+        setter()
+        iteration("after " + setter.__name__)
+    import ctypes as C
+    o.lib.orc_iter_advance.argtypes = [C.c_void_p]
+    h.lib.isg_iter_advance.argtypes = [C.c_void_p]
+    for sweep in {0: ["update_P", "update_Z"], 2: ["update_P", "update_S_POP", "update_G", "update_ZQ"], 3: ["update_P", "update_S_IND", "update_G", "update_ZQ"],
+                  4: ["update_P", "update_S_POP", "update_ZQ"], 5: ["update_P", "update_S_IND", "update_ZQ"]}[mode]:
+        getattr(h, sweep)()
+        getattr(o, sweep)()
+    if mode != 0:   # (mode 0 has neither update_ZQ nor update_alpha)
+        _same(h, o, lkh, "between update_ZQ and update_alpha")   # the previous iteration's
+        h.update_alpha()
+        o.update_alpha()
+    h.cal_lkh()
+    o.cal_lkh()
+    _same(h, o, lkh, "after cal_lkh")
+    _same(h, o, state, "sweep by sweep")
+    o.lib.orc_iter_advance(o.h)
+    h.lib.isg_iter_advance(h.h)
+    assert o.error() == 0
+    h.close()
+
+
+def _tetraploid_read_write_orders(sched, d):
+    """The ploidy 4 oracle is a program that dumps one line per sweep (tests/test_gpu_poly.py) and takes a state -- alpha, the rates, qq -- only
+    right after chain_init (tests/converged_poly.py): the setters are applied there, one chain and one oracle run per setter."""
+    import ctypes as C
+    import converged_poly as cp
+    import test_gpu_poly as tp
+    name = min(tp.EXTRA, key=lambda n: tp.EXTRA[n][0] * tp.EXTRA[n][1])   # the smallest shape generated there
+    N, L, K, A, miss, u, b, t, e, r, j, seeds = tp.EXTRA[name]
+    raw = tp.extra_data(name)
+    obs, alleleid, allelenum = synth.code_tetraploid(raw)
+    txt = os.path.join(d, name + ".txt")
+    synth.write_text_polyploid(txt, raw)
+    nan = np.full((N, K), np.nan)
+
+    def oracle(tag, iters, state=None):
+        out = os.path.join(d, tag + ".can")
+        args = [tp.DUMP, txt, out] + [str(x) for x in (K, N, L, iters, b, t, e, r, iters + 1) + tuple(seeds)] + ["1", "1", str(sched), "0"]
+        if state is not None:
+            cp.write_state(os.path.join(d, tag + ".state"), state)
+            args.append(os.path.join(d, tag + ".state"))
+        assert subprocess.call(args, stdout=subprocess.DEVNULL) == 0
+        return [tp._norm(tp._noseeds(l) if sched else l) for l in gu.parse(out) if l.startswith("it ") or l.startswith("chain zqinit")]
+
+    def chain():
+        ch = capi.HipPolyChain(obs, alleleid, allelenum, K, back_refl=e, rng_sched=sched)
+        ch.setseeds(*seeds)
+        ch.chain_init(np.array([np.float32(ch.ran1()) for _ in range(K)], dtype=np.float32))
+        return ch
+
+    def line(s, ch, seeds_too=True):
+        return tp._norm(s + ("" if sched or not seeds_too else " seeds=%d %d %d" % ch.seeds()))
+
+    def left_by_iteration(ch, step, want, where):   # what an iteration leaves of what its sweeps dumped: the lines of update_ZQ, the genotype sweep and cal_lkh
+        w = [l for l in want if l.startswith("it %d " % step)]
+        assert len(w) == 6, where
+        assert line("it %d GE hgeno=%s" % (step, orc.fnv_i32(ch.geno())), ch) == w[4], where
+        assert line("it %d L totallkh=%s hindv=%s" % (step, float(ch.totallkh()).hex(), orc.fnv_f64(ch.indvlkh())), ch, False) == w[5], where
+        fz = gu.fields(w[3])
+        assert (orc.fnv_i32(ch.z()), orc.fnv_f64(ch.qq()), orc.fnv_f64(ch.qqnum())) == (fz["hz"], fz["hqq"], fz["hqqnum"]), where
+        assert gu.fields(w[0])["hfreq"] == tp._hfreq(ch, allelenum), where
+        assert [float.fromhex(x) if "x" in x else float(x) for x in w[2].split()[3:3 + K]] == [float(x) for x in ch.self_rates()], where
+
+    want = oracle("plain", 2)
+    ch = chain()
+    assert line("chain zqinit hz=%s hqq=%s" % (orc.fnv_i32(ch.z()), orc.fnv_f64(ch.qq())), ch) == want[0]
+    ch.iteration()
+    _twice(ch, ["z", "geno", "count_alleles", "freq", "qq", "qqnum", "self_rates", "state", "indvlkh", "alpha", "totallkh", "seeds"])
+    assert np.array_equal(ch.exfreq(), ch.exfreq()) and np.array_equal(ch.genofreq(), ch.genofreq())
+    left_by_iteration(ch, 0, want, "first")
+    ch.update_P()
+    ch.update_S_POP()
+    ch.update_ZQ(0)   # (ploidy 4 has no update_alpha: the genotype sweep follows)
+    assert line("it 0 L totallkh=%s hindv=%s" % (float(ch.totallkh()).hex(), orc.fnv_f64(ch.indvlkh())), ch, False) == [l for l in want if l.startswith("it 0 L")][0]
+    ch.update_geno()
+    ch.cal_lkh()
+    ch.lib.isg_iter_advance.argtypes = [C.c_void_p]
+    ch.lib.isg_iter_advance(ch.h)
+    left_by_iteration(ch, 1, want, "sweep by sweep")
+    ch.close()
+    for setter in ("set_qq", "set_self_rates", "set_alpha"):
+        ch = chain()
+        if setter == "set_qq":
+            q = 0.5 * ch.qq()[:, ::-1] + 0.5 / K
+            num = ch.qqnum()
+            ch.set_qq(q)
+            assert np.array_equal(ch.qq(), q) and np.array_equal(ch.qqnum(), num)
+            state = cp.State(q, float("nan"), None)
+        elif setter == "set_self_rates":
+            rates = 0.5 * ch.self_rates() + 0.2
+            ch.set_self_rates(rates)
+            assert np.array_equal(ch.self_rates(), rates)
+            state = cp.State(nan, float("nan"), rates)
+        else:
+            a = 0.5 * ch.alpha() + 0.3
+            ch.set_alpha(a)
+            assert ch.alpha() == a
+            state = cp.State(nan, a, None)
+        ch.iteration()
+        left_by_iteration(ch, 0, oracle(setter, 1, state), setter)
+        ch.close()
+
+
+@pytest.mark.parametrize("sched", [capi.SCHED_REPLAY, capi.SCHED_KEYED])
+@pytest.mark.parametrize("kind", [0, 2, 3, 4, 5, "autotetraploid"])
+def test_getters_setters_and_likelihood_reads_in_any_order_bit_exact_vs_canonical_oracle(kind, sched, tmp_path):
+    """The orders of reads and writes no other test takes (which copy of an array is current: the context's host mirrors and their flags, the ahead
+    items of instruct_amd/csrc/isg_ahead.h, the ploidy 4 count tables): a mirror left marked current over a rewritten array fails here.  After chain_init
+    and one iteration every getter is called twice in a row and agrees with itself.  Then every setter the ploidy has is applied to the chain and
+    to the oracle with a changed value, the getter returns it, and the iteration that follows leaves the same state and seeds.  Then one iteration
+    sweep by sweep, with the likelihoods read between update_ZQ and update_alpha (the previous iteration's) and again after cal_lkh."""
+    if kind == "autotetraploid":
+        _tetraploid_read_write_orders(sched, str(tmp_path))
+    else:
+        _diploid_read_write_orders(kind, sched)
+
+
 @pytest.mark.parametrize("persist", ["1", "0"])
 @pytest.mark.parametrize("K", [1, 2, 3, 4, 6, 7, 8])
 def test_replay_block_resolver_every_K_bit_exact(K, persist, monkeypatch):
