@@ -165,6 +165,22 @@ int isg_store_begin(isg_ctx *ctx, int with_freq);
 int isg_store_step(isg_ctx *ctx);
 int isg_store_fetch(isg_ctx *ctx, double *qq, double *qq2, double *indvlkh, double *gen, double *gen2, double *freq, double *freq2, long *steps);
 
+/* Posterior co-ancestry on the device: C[i][j] = (1/S) sum over the S accumulated steps of sum_k qq[i][k] qq[j][k] (mode 0: of
+ * 1[zz[i] == zz[j]]), the probability that an allele copy of i and one of j come from the same cluster.  It does not change when the
+ * clusters are relabelled, so chains can be averaged entry by entry (instruct_amd/coanc.py).  Every context kind, both schedules.
+ * isg_coanc_begin allocates a dense [N][N] double sum and a history of `batch` snapshots of Q (0: the library's default) and fails,
+ * naming the size, when the two exceed half of the free device memory; called again it restarts from zero.  isg_coanc_step copies
+ * the current Q into the history on the launch stream (no host copy, no synchronisation) and, when `batch` snapshots are held,
+ * adds their products to the sum with the f64 matrix instruction (k_coanc_snap, k_coanc_syrk; DESIGN.md "Posterior co-ancestry").
+ * isg_coanc_fetch adds what is held, then returns sum / steps as a symmetric [N][N] matrix and the step count; accumulation may go
+ * on afterwards.  It fails before the first step.  isg_coanc_end releases the buffers (isg_ctx_destroy does the same).  No entry
+ * point writes chain state or consumes random numbers.  The same calls give the same bits; sums whose products and partial sums
+ * are all representable are exact; nothing is promised about the order of the additions otherwise. */
+int isg_coanc_begin(isg_ctx *ctx, int batch);
+int isg_coanc_step(isg_ctx *ctx);
+int isg_coanc_fetch(isg_ctx *ctx, double *mean, long *steps);
+int isg_coanc_end(isg_ctx *ctx);
+
 /* Replay-schedule update_ZQ runs as several cooperating workgroups that hand counts to each other by polling.  If such a
  * sweep cannot complete (the GPU is shared and a workgroup was not scheduled in time, or a Dirichlet ran past the uniform
  * budget) it is redone from the same stream position by the single-workgroup kernel: same results, only slower.  This

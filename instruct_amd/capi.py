@@ -25,6 +25,7 @@ EXPORTS = [
     "isg_set_generation", "isg_set_self_rates", "isg_set_alpha", "isg_keyed_layout", "isg_profile_enable",
     "isg_profile_count", "isg_profile_get", "isg_profile_reset", "isg_gelman_rubin", "isg_selftest",
     "isg_store_begin", "isg_store_step", "isg_store_fetch", "isg_zq_fallbacks", "isg_p_device_stats", "isg_zq_spec_stats", "isg_copy_bandwidth", "isg_diag_live_buffers", "isg_zq_resolve_stats", "isg_zq_resolve_plan", "isg_gather_convg",
+    "isg_coanc_begin", "isg_coanc_step", "isg_coanc_fetch", "isg_coanc_end",
     "isg_ctx_create_poly", "isg_poly_update_geno", "isg_get_poly_geno", "isg_get_poly_gs", "isg_get_poly_table", "isg_get_poly_freq2",
 ]
 
@@ -233,6 +234,24 @@ class HipChain:
         self._chk(self.lib.isg_store_fetch(self.h, *args, C.byref(steps)))
         out["steps"] = steps.value
         return out
+
+    # --- posterior co-ancestry on the device (isg_coanc_*, DESIGN.md "Posterior co-ancestry")
+    def coanc_begin(self, batch=0):
+        """start (or restart from zero) accumulating C[i][j] = mean over steps of sum_k qq[i][k] qq[j][k]; batch: snapshots per flush, 0 = default"""
+        self._chk(self.lib.isg_coanc_begin(self.h, int(batch)))
+
+    def coanc_step(self):
+        self._chk(self.lib.isg_coanc_step(self.h))
+
+    def coanc_fetch(self):
+        """(mean ndarray [N][N], steps); accumulation may go on afterwards"""
+        mean = np.empty((self.N, self.N), dtype=np.float64)
+        steps = C.c_long()
+        self._chk(self.lib.isg_coanc_fetch(self.h, _ptr(mean), C.byref(steps)))
+        return mean, steps.value
+
+    def coanc_end(self):
+        self._chk(self.lib.isg_coanc_end(self.h))
 
     def zq_fallbacks(self):
         """replay update_ZQ sweeps that were redone by the single-workgroup kernel (see include/instruct_hip.h)"""

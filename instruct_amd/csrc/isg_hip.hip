@@ -48,6 +48,7 @@
 #include "isg_kdispatch.h"
 #include "isg_devbuf.h"
 #include "isg_ahead.h"
+#include "isg_coanc.h"
 
 #define ISG_KCAP 32  /* K of the register-resident kernel instances, and of ploidy 4 */
 #define ISG_KWIDE 64 /* diploid K above ISG_KCAP: the K-generic wide kernels (DESIGN.md §4 "K up to 64") */
@@ -171,6 +172,8 @@ struct CtxBufs {
 	/* CHAIN running means kept on the device (isg_store_*): qq, qq2 [N][K]; indvlkh, gen, gen2 [N]; freq, freq2 in the
 	 * device order of d.freq */
 	DevBuf<double> st_qq, st_qq2, st_lkh, st_gen, st_gen2, st_freq, st_freq2;
+	/* posterior co-ancestry (isg_coanc_*): the snapshot history [batch][Np][Kp] and the [N][N] sum */
+	DevBuf<double> co_hist, co_acc;
 };
 struct isg_ctx : CtxBufs {
 	isg_config cfg;
@@ -230,6 +233,9 @@ struct isg_ctx : CtxBufs {
 	bool h_qq, h_gen, h_S, h_lkh;
 	long st_step = 0;
 	bool st_on = false;
+	bool co_on = false;        /* isg_coanc_begin has run */
+	int co_batch = 0, co_held = 0; /* snapshots per flush; snapshots in the history not yet in the sum */
+	long co_steps = 0;
 	/* profiling */
 	bool prof;
 	std::vector<ProfEntry> prof_entries;
@@ -3278,6 +3284,8 @@ extern "C" int isg_store_fetch(isg_ctx *c, double *qq, double *qq2, double *indv
 	if (steps) *steps = c->st_step;
 	return 0;
 }
+
+#include "isg_coanc_hip.inc"
 
 extern "C" long isg_zq_fallbacks(isg_ctx *c) { return c->zq_fallbacks; }
 extern "C" int isg_zq_spec_stats(isg_ctx *c, long out[10])

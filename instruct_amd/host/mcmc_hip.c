@@ -13,6 +13,8 @@
  * reference run.
  *
  * Environment: INSTRUCT_GPU_RNG=replay|keyed (default replay), INSTRUCT_DEVICE=<ordinal>.
+ * INSTRUCT_COANC_OUT=<prefix>: every chain that finishes also writes its posterior co-ancestry matrix (isg_coanc_*, accumulated on the
+ * device at the stored steps) to <prefix>.chain<n>.coanc -- see coanc_write() below; unset: no isg_coanc_* function is called.
  * Set by the multi-GPU launcher (instruct_mgpu.c), one process per chain: INSTRUCT_MGPU_RANK, INSTRUCT_MGPU_WORLD,
  * INSTRUCT_MGPU_DIR (rendezvous directory), INSTRUCT_MGPU_GATHER=rccl|file -- see mgpu_exchange() below.
  */
@@ -447,6 +449,37 @@ static isg_ctx *get_ctx(SEQDATA d)
 	return g_ctx;
 }
 
+/* INSTRUCT_COANC_OUT: the posterior co-ancestry matrix of a finished chain, C[i][j] = mean over the stored steps of sum_k qq[i][k] qq[j][k]
+ * (mode 0: of 1[zz[i] == zz[j]]).  File <prefix>.chain<chn + 1>.coanc, little endian: 8 bytes "ISGCOANC", int64 N, int64 steps, then the
+ * lower triangle of the mean as N (N + 1) / 2 doubles, row-major (row i: columns 0 .. i).  instruct_amd/coanc.py reads and combines
+ * such files.  Nothing goes to stdout or to the result file. */
+static const char *coanc_prefix(void)
+{
+	const char *e = getenv("INSTRUCT_COANC_OUT");
+	return (e && *e) ? e : NULL;
+}
+static void coanc_write(isg_ctx *ctx, const char *prefix, int chn, int N)
+{
+	double *m = (double *)malloc(sizeof(double) * (size_t)N * N);
+	char *path = (char *)malloc(strlen(prefix) + 64);
+	long steps = 0;
+	int64_t head[2];
+	FILE *fp;
+	int i;
+	if (!m || !path) nrerror("allocation failure for the co-ancestry matrix");
+	if (isg_coanc_fetch(ctx, m, &steps)) hip_fail("isg_coanc_fetch");
+	sprintf(path, "%s.chain%d.coanc", prefix, chn + 1);
+	if ((fp = fopen(path, "wb")) == NULL) nrerror("cannot open the co-ancestry file named by INSTRUCT_COANC_OUT");
+	head[0] = N;
+	head[1] = steps;
+	if (fwrite("ISGCOANC", 1, 8, fp) != 8 || fwrite(head, sizeof(int64_t), 2, fp) != 2) nrerror("cannot write the co-ancestry file");
+	for (i = 0; i < N; i++)
+		if (fwrite(m + (size_t)i * N, sizeof(double), (size_t)i + 1, fp) != (size_t)i + 1) nrerror("cannot write the co-ancestry file");
+	if (fclose(fp)) nrerror("cannot write the co-ancestry file");
+	free(path);
+	free(m);
+}
+
 /* mcmc_POP_admixture (mcmc.c:135-179), mcmc_POP_selfing (mcmc.c:182-239) and, for ploidy 4 with -ap 1,
  * mcmc_POP_tetra_selfing (poly_geno.c:75-140; that driver has no free_space() epilogue) */
 static CHAIN mcmc_hip_chain(SEQDATA data, INIT initial, int chn, CONVG *cvg)
@@ -461,6 +494,7 @@ static CHAIN mcmc_hip_chain(SEQDATA data, INIT initial, int chn, CONVG *cvg)
 	const int tetra = (data.ploid == 4), inbr = (data.ploid == 2 && data.mode == 4), indv = (data.ploid == 2 && data.mode == 3),
 		  finb = (data.ploid == 2 && data.mode == 5);
 	int i, j, k, stored_on_device = 0;
+	const char *coanc = coanc_prefix();
 
 	memset(&mchain, 0, sizeof(mchain));
 	memset(&node, 0, sizeof(node));
@@ -523,10 +557,12 @@ static CHAIN mcmc_hip_chain(SEQDATA data, INIT initial, int chn, CONVG *cvg)
 			allocate_chn(&mchain, data);
 			if (isg_store_begin(ctx, data.print_freq == 1 && !tetra)) hip_fail("isg_store_begin");
 			stored_on_device = 1;
+			if (coanc && isg_coanc_begin(ctx, 0)) hip_fail("isg_coanc_begin");
 		}
 		if (stored) {
 			/* store_chn (mcmc.c:1320-1456): qq, qq2, indvlkh, gen, gen2, freq, freq2 on the device, the rest here */
 			if (isg_store_step(ctx)) hip_fail("isg_store_step");
+			if (coanc && isg_coanc_step(ctx)) hip_fail("isg_coanc_step");
 			store_chn_small(&mchain, &node, data);
 			if (cnt_step < cvg->ckrep) cvg->convg_ld[chn * cvg->ckrep + cnt_step] = node.totallkh;
 			cnt_step++;
@@ -570,6 +606,10 @@ static CHAIN mcmc_hip_chain(SEQDATA data, INIT initial, int chn, CONVG *cvg)
 		free(q1);
 		free(q2);
 		free(f2);
+		if (coanc) { /* a chain discarded for an empty cluster writes no file */
+			if (mchain.flag_empty_cluster == 0 && cnt_step > 0) coanc_write(ctx, coanc, chn, N);
+			if (isg_coanc_end(ctx)) hip_fail("isg_coanc_end");
+		}
 	}
 
 	free_dmatrix(node.qq, 0, N - 1, 0, K - 1);
@@ -603,7 +643,8 @@ static CHAIN mcmc_hip_chain0(SEQDATA data, INIT initial, int chn, CONVG *cvg)
 	long seeds[3], cnt_step = 0, step;
 	const int N = data.totalsize, K = data.popnum, L = data.locinum, A = data.allelenum_max;
 	double *freqflat = data.print_freq == 1 ? (double *)malloc(sizeof(double) * (size_t)K * L * A) : NULL;
-	int i, j, k;
+	int i, j, k, coanc_on = 0;
+	const char *coanc = coanc_prefix();
 	memset(&mchain, 0, sizeof(mchain));
 	memset(&node, 0, sizeof(node));
 	if (data.print_freq == 1) node.freq = d3tensor(0, K - 1, 0, L - 1, 0, A - 1);
@@ -625,8 +666,15 @@ static CHAIN mcmc_hip_chain0(SEQDATA data, INIT initial, int chn, CONVG *cvg)
 			node.totallkh = ref_nan(node.totallkh);
 		}
 		if (data.print_iter == 1) print_info(&node, data, step, initial.update);
-		if (step == initial.burnin - 1) allocate_chn(&mchain, data);
+		if (step == initial.burnin - 1) {
+			allocate_chn(&mchain, data);
+			if (coanc) {
+				if (isg_coanc_begin(ctx, 0)) hip_fail("isg_coanc_begin");
+				coanc_on = 1;
+			}
+		}
 		if (stored) {
+			if (coanc_on && isg_coanc_step(ctx)) hip_fail("isg_coanc_step");
 			isg_get_indvlkh(ctx, node.indvlkh);
 			isg_get_generation(ctx, node.zz); /* the ABI returns the cluster of each individual in the generation slots */
 			if (data.print_freq == 1) {
@@ -643,6 +691,10 @@ static CHAIN mcmc_hip_chain0(SEQDATA data, INIT initial, int chn, CONVG *cvg)
 	isg_get_seeds(ctx, seeds);
 	setseeds((int)seeds[0], (int)seeds[1], (int)seeds[2]);
 	mgpu_exchange(ctx, cvg, chn);
+	if (coanc_on) {
+		if (cnt_step > 0) coanc_write(ctx, coanc, chn, N);
+		if (isg_coanc_end(ctx)) hip_fail("isg_coanc_end");
+	}
 	free_ivector(node.zz, 0, N - 1);
 	free_dvector(node.indvlkh, 0, N - 1);
 	if (data.print_freq == 1) free_d3tensor(node.freq, 0, K - 1, 0, L - 1, 0, A - 1);
