@@ -236,6 +236,11 @@ long isg_diag_live_buffers(void);
  * quotient by reciprocal + fma, table skip-ahead) against the plain formulas of random.c:19-47 */
 int isg_selftest(void);
 
+/* the single precision generator step and uniform (isg_whf_step, isg_whf_value_f32: what the sweeps' inner loops run) evaluated on
+ * `device`, one launch with a thread per state of each of the three generators: the number of states at which the device's results
+ * differ from the host's or from the plain formula (0 on a correct build), -1 on a HIP error (isg_last_error) */
+int isg_selftest_device(int device);
+
 /* Chains sharded one per GPU (the reference runs them back to back, InStruct.c:182-193): the only exchange is each chain's
  * n stored log-likelihood samples (CONVG.convg_ld, mcmc.c:223-224).  isg_gather_convg: ONE ncclAllGather over RCCL / xGMI
  * on device buffers; all[r * n + k] = sample k of rank r.  id_path: a file every rank can reach (rank 0 publishes the

@@ -23,7 +23,7 @@ EXPORTS = [
     "isg_get_qqnum", "isg_get_generation", "isg_get_self_rates", "isg_get_state", "isg_get_indvlkh",
     "isg_get_alpha", "isg_get_totallkh", "isg_get_amax", "isg_set_z", "isg_set_freq", "isg_set_qq",
     "isg_set_generation", "isg_set_self_rates", "isg_set_alpha", "isg_keyed_layout", "isg_profile_enable",
-    "isg_profile_count", "isg_profile_get", "isg_profile_reset", "isg_gelman_rubin", "isg_selftest",
+    "isg_profile_count", "isg_profile_get", "isg_profile_reset", "isg_gelman_rubin", "isg_selftest", "isg_selftest_device",
     "isg_store_begin", "isg_store_step", "isg_store_fetch", "isg_zq_fallbacks", "isg_p_device_stats", "isg_zq_spec_stats", "isg_copy_bandwidth", "isg_diag_live_buffers", "isg_zq_resolve_stats", "isg_zq_resolve_plan", "isg_gather_convg",
     "isg_coanc_begin", "isg_coanc_step", "isg_coanc_fetch", "isg_coanc_end",
     "isg_ctx_create_poly", "isg_poly_update_geno", "isg_get_poly_geno", "isg_get_poly_gs", "isg_get_poly_table", "isg_get_poly_freq2",
@@ -365,6 +365,17 @@ def copy_bandwidth(device=0, nbytes=1 << 30, reps=8):
     if lib.isg_copy_bandwidth(device, nbytes, reps, C.byref(g)) != 0:
         raise IsgError(lib.isg_last_error().decode())
     return g.value
+
+
+def selftest_device(device=0):
+    """states of the three generators at which the DEVICE's single precision step or uniform differs from the host's
+    (isg_selftest_device: one launch, a thread per state); 0 on a correct build"""
+    lib = load()
+    lib.isg_selftest_device.argtypes = [C.c_int]
+    n = lib.isg_selftest_device(device)
+    if n < 0:
+        raise IsgError(lib.isg_last_error().decode())
+    return n
 
 
 def live_buffers():

@@ -1206,7 +1206,8 @@ zq_one(const DevView &d, ZqShared &sh, int i, isg_wh cur, unsigned long long off
 	const uint8_t *grow = d.geno + (size_t)i * rowb;
 	uint8_t *zrow = d.z + (size_t)i * rowb;
 	unsigned running = 0;
-	isg_wh mult = mult0;
+	isg_wh pstart = mult0; /* (fast path, K <= 8) the lane's state at the start of the pass, carried from pass to pass */
+	isg_wh mult = mult0;   /* (fast path, K > 8) the multiplier from `cur` to it */
 	for (int jb = 0; jb < d.Lp; jb += BLOCK * ISG_LPT) {
 		const int j0 = jb + t * ISG_LPT;
 		unsigned long long gnext = ~0ull;
@@ -1247,12 +1248,14 @@ zq_one(const DevView &d, ZqShared &sh, int i, isg_wh cur, unsigned long long off
 			rank = running + block_excl_scan<BLOCK>(nv, sh.scan, &tot);
 			running += tot;
 		}
-		/* `x` holds the exact uniforms when they come from the tape; when they are generated here only
-		 * the packed generator states are kept: the float pre-filter needs a float value, the exact
-		 * double is formed just for the few draws that are redone */
+		/* `x` holds the exact uniforms when they come from the tape.  When they are generated here the generator is
+		 * stepped in single precision (isg_whf): the float pre-filter needs a float value, and for the few draws that
+		 * are redone the copy's state is stepped to again from the lane's state at the start of the pass (`s0f`), so
+		 * no per-copy state is kept (exact_x below).  Without the pre-filter (K > 8) the packed states `st` are. */
 		double x[2 * ISG_LPT];
 		float xf[2 * ISG_LPT];
-		unsigned long long st[2 * ISG_LPT];
+		isg_whf s0f = {0.f, 0.f, 0.f};
+		unsigned long long st[HOIST ? 1 : 2 * ISG_LPT];
 		if (taped) {
 			const double *tp = d.tape + off + 2ull * rank;
 			unsigned k = 0;
@@ -1265,7 +1268,40 @@ zq_one(const DevView &d, ZqShared &sh, int i, isg_wh cur, unsigned long long off
 				xf[2 * l + 1] = (float)x[2 * l + 1];
 				k += valid ? 2u : 0u;
 			}
+		} else if constexpr (HOIST) {
+			isg_wh s0;
+			if (fast) {
+				/* nothing missing: the lane's state at the start of a pass is the one a pass earlier, BLOCK * ISG_LPT loci on */
+				s0 = pstart = isg_wh_mul(jb == 0 ? cur : pstart, jb == 0 ? mult0 : mult_pass); /* one product a pass */
+			} else {
+				s0 = isg_wh_jump32(&sh.tab, cur, 2u * rank);
+			}
+			isg_whf s = s0f = isg_whf_of(s0);
+			if (fast) {
+				/* only the padded loci behind L are unused, and the states behind them are never used again: no select */
+#pragma unroll
+				for (int c8 = 0; c8 < 2 * ISG_LPT; c8++) {
+					isg_whf_step(&s);
+					xf[c8] = isg_whf_value_f32(&s);
+				}
+			} else {
+#pragma unroll
+				for (int l = 0; l < ISG_LPT; l++) {
+					const bool valid = (((unsigned)(gb >> (16 * l)) & 0xff) != 0xff);
+					isg_whf s2 = s;
+#pragma unroll
+					for (int cp = 0; cp < 2; cp++) {
+						isg_whf_step(&s2);
+						xf[2 * l + cp] = isg_whf_value_f32(&s2);
+					}
+					s.s1 = valid ? s2.s1 : s.s1; /* unused loci consume nothing (mcmc.c:1137) */
+					s.s2 = valid ? s2.s2 : s.s2;
+					s.s3 = valid ? s2.s3 : s.s3;
+				}
+			}
 		} else {
+			/* K > 8: every draw is decided in double and no single precision value is wanted, so the generator keeps its integer
+			 * form (the float step's constants would only occupy registers here) and the packed states of the copies */
 			isg_wh s;
 			if (fast) {
 				s = isg_wh_mul(cur, mult);
@@ -1281,20 +1317,28 @@ zq_one(const DevView &d, ZqShared &sh, int i, isg_wh cur, unsigned long long off
 				for (int cp = 0; cp < 2; cp++) {
 					isg_wh_step(&s2);
 					st[2 * l + cp] = (unsigned long long)s2.s1 | ((unsigned long long)s2.s2 << 16) | ((unsigned long long)s2.s3 << 32);
-					xf[2 * l + cp] = isg_wh_value_f32(&s2);
 				}
 				s.s1 = valid ? s2.s1 : s.s1; /* unused loci consume nothing (mcmc.c:1137) */
 				s.s2 = valid ? s2.s2 : s.s2;
 				s.s3 = valid ? s2.s3 : s.s3;
 			}
 		}
+		/* the exact uniform of copy c8: with the pre-filter it is wanted for a few draws in 10^5, and the copy's state is re-derived */
 		auto exact_x = [&](int c8) -> double {
 			if (taped) return x[c8];
-			isg_wh e;
-			e.s1 = (uint32_t)(st[c8] & 0xffff);
-			e.s2 = (uint32_t)((st[c8] >> 16) & 0xffff);
-			e.s3 = (uint32_t)((st[c8] >> 32) & 0xffff);
-			return isg_wh_value(&e);
+			if constexpr (HOIST) {
+				unsigned vmask = 0;
+#pragma unroll
+				for (int l = 0; l < ISG_LPT; l++) vmask |= ((((unsigned)(gb >> (16 * l)) & 0xff) != 0xff) ? 1u : 0u) << l;
+				const isg_whf e = isg_whf_copy_state(s0f, vmask, c8);
+				return isg_whf_value(&e);
+			} else {
+				isg_wh e;
+				e.s1 = (uint32_t)(st[c8] & 0xffff);
+				e.s2 = (uint32_t)((st[c8] >> 16) & 0xffff);
+				e.s3 = (uint32_t)((st[c8] >> 32) & 0xffff);
+				return isg_wh_value(&e);
+			}
 		};
 		/* phase 3: buckets.  Straight-line float pre-filter over the 8 copies; flagged draws are redone
 		 * in double afterwards (rare), so no data-dependent branch sits between the dependency chains. */
@@ -3379,6 +3423,12 @@ extern "C" int isg_selftest(void)
 		for (uint32_t s = 0; s < M[g] + 2000; s++) {
 			if (isg_lcg_fast(s, A[g], M[g], inv) != (A[g] * s) % M[g]) return fail("isg_selftest: isg_lcg_fast differs from (a*s) % m");
 			if (isg_wh_div(s, md, invd) != (double)s / md) return fail("isg_selftest: isg_wh_div differs from s / m");
+			/* the single precision step (isg_whf_step's): the integer result as an integer-valued float, bit for bit */
+			volatile float sf = (float)s;
+			isg_whf f = {sf, sf, sf};
+			isg_whf_step(&f);
+			const float r = g == 0 ? f.s1 : (g == 1 ? f.s2 : f.s3);
+			if (isg_f2u(r) != isg_f2u((float)((A[g] * s) % M[g]))) return fail("isg_selftest: isg_whf_step differs from (a*s) % m");
 		}
 	}
 	isg_wh_tables tab;
@@ -3392,6 +3442,57 @@ extern "C" int isg_selftest(void)
 		}
 	}
 	return 0;
+}
+
+/* ---- the same on the device: isg_whf_step and isg_whf_value_f32 as the GPU evaluates them, a thread per state ---- */
+#define ISG_WHF_NSTATES (ISG_M1 + ISG_M2 + ISG_M3)
+/* state k: generator g's component runs over [0, m_g); the other two are filled from it so that the uniform's sum has three terms */
+ISG_HD isg_whf whf_selftest_state(uint32_t k)
+{
+	isg_wh w;
+	if (k < ISG_M1) { w.s1 = k; w.s2 = (7u * k + 3u) % ISG_M2; w.s3 = (11u * k + 5u) % ISG_M3; }
+	else if (k < ISG_M1 + ISG_M2) { k -= ISG_M1; w.s2 = k; w.s1 = (7u * k + 3u) % ISG_M1; w.s3 = (11u * k + 5u) % ISG_M3; }
+	else { k -= ISG_M1 + ISG_M2; w.s3 = k; w.s1 = (7u * k + 3u) % ISG_M1; w.s2 = (11u * k + 5u) % ISG_M2; }
+	return isg_whf_of(w);
+}
+ISG_HD uint4 whf_selftest_eval(uint32_t k)
+{
+	isg_whf f = whf_selftest_state(k);
+	isg_whf_step(&f);
+	uint4 r;
+	r.x = isg_f2u(f.s1); r.y = isg_f2u(f.s2); r.z = isg_f2u(f.s3); r.w = isg_f2u(isg_whf_value_f32(&f));
+	return r;
+}
+__global__ void __launch_bounds__(256) k_whf_selftest(uint4 *out, uint32_t n)
+{
+	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+	if (k < n) out[k] = whf_selftest_eval(k);
+}
+static int whf_selftest_device(int device, long *bad)
+{
+	const uint32_t n = ISG_WHF_NSTATES;
+	HIPCHK(hipSetDevice(device));
+	DevBuf<uint4> out;
+	HIPCHK(out.alloc(n));
+	hipLaunchKernelGGL(k_whf_selftest, dim3((n + 255u) / 256u), dim3(256), 0, 0, out.get(), n);
+	HIPCHK(hipGetLastError());
+	std::vector<uint4> got(n);
+	HIPCHK(hipMemcpy(got.data(), out.get(), (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost));
+	*bad = 0;
+	for (uint32_t k = 0; k < n; k++) {
+		const uint4 w = whf_selftest_eval(k);
+		const isg_wh s = isg_whf_to(whf_selftest_state(k));
+		const bool plain = w.x == isg_f2u((float)(ISG_A1 * s.s1 % ISG_M1)) && w.y == isg_f2u((float)(ISG_A2 * s.s2 % ISG_M2)) && w.z == isg_f2u((float)(ISG_A3 * s.s3 % ISG_M3));
+		if (!plain || got[k].x != w.x || got[k].y != w.y || got[k].z != w.z || got[k].w != w.w) ++*bad;
+	}
+	return 0;
+}
+/* states at which the device's step or single precision uniform differs from the host's (or either from the plain formula); -1: HIP error */
+extern "C" int isg_selftest_device(int device)
+{
+	long bad = 0;
+	if (whf_selftest_device(device, &bad) != 0) return -1;
+	return (int)bad;
 }
 
 #include "isg_rccl.inc"

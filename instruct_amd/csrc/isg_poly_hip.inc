@@ -926,15 +926,19 @@ __device__ __forceinline__ unsigned k4_zq_one(const PolyDev &p, const DevView &d
 		int zz[4] = {0xff, 0xff, 0xff, 0xff};
 		if (valid) {
 			const unsigned rank = p.rankwave[(size_t)i * p.nwv + (j >> 6)] + (unsigned)__popcll(vm & ((1ull << lane_id()) - 1ull));
-			isg_wh s = isg_wh_jump32(&sh.tab, cur, 4u * rank);
+			constexpr bool PREF = (KMAX <= 16); /* instances with the single precision pre-filter */
+			isg_wh si = isg_wh_jump32(&sh.tab, cur, 4u * rank);
+			isg_whf s = isg_whf_of(si);
 			const unsigned g = *(const unsigned *)(p.geno + id * 4);
 			zout = 0;
 			for (int c = 0; c < 4; c++) {
-				/* the pre-filter takes the uniform's single precision value (|error| < 1e-6: inside bucket_f32's band, as in the diploid zq_one); the
-				 * exact value (three double precision divisions) only in the draws that are redone */
-				isg_wh_step(&s);
+				/* the pre-filter takes the uniform's single precision value (|error| < 1e-6: inside bucket_f32's band, as in the diploid zq_one), from
+				 * the generator stepped in single precision (isg_whf); the exact value (three double precision divisions) only in the draws that
+				 * are redone.  Without a pre-filter (KMAX > 16) every draw takes the exact value: the integer step stays */
+				if (PREF) isg_whf_step(&s);
+				else isg_wh_step(&si);
 				if (init_flag) {
-					zz[c] = k4_draw_init<KMAX>(s, K);
+					zz[c] = k4_draw_init<KMAX>(PREF ? isg_whf_to(s) : si, K);
 				} else {
 					bool amb = true;
 					if (KMAX <= 16) { /* single precision pre-filter (see bucket_f32); flagged draws redone in double */
@@ -955,9 +959,9 @@ __device__ __forceinline__ unsigned k4_zq_one(const PolyDev &p, const DevView &d
 								if (m + 3 < KMAX) F[m + 3] = 0.f;
 							}
 						}
-						zz[c] = bucket_f32<KMAX>(isg_wh_value_f32(&s), F, qf, K, &amb);
+						zz[c] = bucket_f32<KMAX>(isg_whf_value_f32(&s), F, qf, K, &amb);
 					}
-					if (amb) zz[c] = k4_draw_exact<KMAX>(&p, i, j, (g >> (8 * c)) & 0xff, s, K);
+					if (amb) zz[c] = k4_draw_exact<KMAX>(&p, i, j, (g >> (8 * c)) & 0xff, PREF ? isg_whf_to(s) : si, K);
 				}
 				zout |= (unsigned)zz[c] << (8 * c);
 			}

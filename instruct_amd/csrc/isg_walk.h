@@ -439,10 +439,19 @@ ISG_HD void wk_table_body(const WkTableArgs A, int wg, int nthreads, unsigned ch
 		} else {
 			for (int i0 = tlo + t * 16; i0 < thi; i0 += nthreads * 16) { /* 16 per skip-ahead */
 				isg_wh s = isg_wh_jump(A.tab, A.base, s0 + (unsigned long long)i0);
-				for (int k = 0; k < 16 && i0 + k < thi; k++) {
-					isg_wh_step(&s);
-					/* interval mode: the bits are speculation anyway, the cheaper single precision evaluation (error < 1e-6) will do */
-					tape[i0 + k] = interval ? isg_wh_value_f32(&s) : (float)isg_wh_value(&s);
+				if (interval) {
+					/* the bits are speculation anyway, the cheaper single precision evaluation (error < 1e-6) will do: the
+					 * generator is stepped in single precision too (isg_whf: the same states, the same bits) */
+					isg_whf f = isg_whf_of(s);
+					for (int k = 0; k < 16 && i0 + k < thi; k++) {
+						isg_whf_step(&f);
+						tape[i0 + k] = isg_whf_value_f32(&f);
+					}
+				} else {
+					for (int k = 0; k < 16 && i0 + k < thi; k++) {
+						isg_wh_step(&s);
+						tape[i0 + k] = (float)isg_wh_value(&s);
+					}
 				}
 			}
 		}

@@ -116,6 +116,114 @@ ISG_HD float isg_wh_value_f32(const isg_wh *s)
 	return x;
 }
 
+/*
+ * The same generator with its state held in single precision: the sweeps' inner loops step in this form, which needs no
+ * integer <-> float conversion on the way to the single precision uniform (DESIGN.md "The generator in single precision").  Every
+ * component is an integer-valued float in [0, m); all of the arithmetic below is exact, so the state sequence is the integer
+ * one and isg_whf_value_f32 gives isg_wh_value_f32's bits.  Host and device run the same code.
+ */
+typedef struct {
+	float s1, s2, s3;
+} isg_whf;
+
+ISG_HD uint32_t isg_f2u(float x)
+{
+	union { float f; uint32_t u; } c;
+	c.f = x;
+	return c.u;
+}
+ISG_HD float isg_u2f(uint32_t u)
+{
+	union { float f; uint32_t u; } c;
+	c.u = u;
+	return c.f;
+}
+
+/* 1/m rounded, then lowered by 2^-20 of itself: floor(p * inv) is never above floor(p / m) and at most one below it for
+ * the integers p < 2^24 (exhaustive check: isg_selftest(), tests/test_whf_step.py) */
+#define ISG_INVLO1 ((float)((1.0 / 30269.0) * (1.0 - 0x1p-20)))
+#define ISG_INVLO2 ((float)((1.0 / 30307.0) * (1.0 - 0x1p-20)))
+#define ISG_INVLO3 ((float)((1.0 / 30323.0) * (1.0 - 0x1p-20)))
+
+/* (a * s) mod m for an integer-valued s in [0, m + 2000): a * s < 2^24 is exact, so is the fma's remainder in [0, 2m); a
+ * negative r - m has its sign bit set and loses the comparison of the bit patterns as unsigned numbers, so that comparison
+ * is the one correction */
+ISG_HD float isg_lcgf(float s, float a, float m, float inv_lo)
+{
+	const float p = a * s;
+	const float q = __builtin_floorf(p * inv_lo);
+	const float r = __builtin_fmaf(-q, m, p);
+	const uint32_t u = isg_f2u(r), v = isg_f2u(r - m);
+	return isg_u2f(u < v ? u : v);
+}
+
+/* (states at or above the modulus are reduced first, as isg_wh_jump does) */
+ISG_HD isg_whf isg_whf_from(isg_wh s)
+{
+	isg_whf f;
+	f.s1 = (float)(s.s1 % ISG_M1);
+	f.s2 = (float)(s.s2 % ISG_M2);
+	f.s3 = (float)(s.s3 % ISG_M3);
+	return f;
+}
+/* the same for a state known to be below the moduli (a result of isg_wh_mul or of a skip-ahead) */
+ISG_HD isg_whf isg_whf_of(isg_wh s)
+{
+	isg_whf f;
+	f.s1 = (float)s.s1;
+	f.s2 = (float)s.s2;
+	f.s3 = (float)s.s3;
+	return f;
+}
+ISG_HD isg_wh isg_whf_to(isg_whf f)
+{
+	isg_wh s;
+	s.s1 = (uint32_t)f.s1;
+	s.s2 = (uint32_t)f.s2;
+	s.s3 = (uint32_t)f.s3;
+	return s;
+}
+ISG_HD void isg_whf_step(isg_whf *s)
+{
+	s->s1 = isg_lcgf(s->s1, (float)ISG_A1, (float)ISG_M1, ISG_INVLO1);
+	s->s2 = isg_lcgf(s->s2, (float)ISG_A2, (float)ISG_M2, ISG_INVLO2);
+	s->s3 = isg_lcgf(s->s3, (float)ISG_A3, (float)ISG_M3, ISG_INVLO3);
+}
+/* isg_wh_value_f32's expression, term for term: (float)s of the integer state is the float held here */
+ISG_HD float isg_whf_value_f32(const isg_whf *s)
+{
+	float x = s->s1 * (1.0f / 30269.0f) + s->s2 * (1.0f / 30307.0f) + s->s3 * (1.0f / 30323.0f);
+	x = (x >= 2.0f) ? x - 2.0f : ((x >= 1.0f) ? x - 1.0f : x);
+	return x;
+}
+/* the exact uniform (for the few draws that are re-taken in double) */
+ISG_HD double isg_whf_value(const isg_whf *s)
+{
+	const isg_wh e = isg_whf_to(*s);
+	return isg_wh_value(&e);
+}
+
+/*
+ * update_ZQ's pass (zq_one) walks a lane's loci in order, two steps per locus, and an unused locus hands its predecessor's state
+ * on (it consumes nothing).  The pass keeps no per-copy states: for the few draws it re-takes in double it asks for the state of
+ * copy c8 (locus c8 / 2, copy c8 % 2) again, from the lane's state at the start of the pass and the mask of its used loci
+ * (bit l = locus l is used).  Locus c8 / 2 itself is stepped whether used or not, as the pass does.
+ */
+ISG_HD isg_whf isg_whf_copy_state(isg_whf start, unsigned vmask, int c8)
+{
+	isg_whf s = start;
+	int l;
+	for (l = 0; l < (c8 >> 1); l++) {
+		if ((vmask >> l) & 1u) {
+			isg_whf_step(&s);
+			isg_whf_step(&s);
+		}
+	}
+	isg_whf_step(&s);
+	if (c8 & 1) isg_whf_step(&s);
+	return s;
+}
+
 ISG_HD double isg_wh_next(isg_wh *s)
 {
 	isg_wh_step(s);
